@@ -1,19 +1,29 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the continuous-clustering hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[2], the throughput configuration of the metric "Mpoints/s clustered (64-beam
 stream)"): 256 concurrent synthetic S64 sensor streams per GPU (64 rows x 2200 columns per rotation, KITTI
 parameters of src/tools/kitti_demo.cpp:279-294, seeded scenes of SURVEY.md 8d, sensor translating at 10 m/s).
 One *step* = one pass of the hot path (insertion -> ground segmentation -> association / union-find ->
 finished-cluster check -> publish) over one batch = one rotation (2200 firings) of every stream. Inputs are
-generated directly in HBM before the timed region. value = published range-image cells per second (NaN cells
+generated directly in HBM before the timed region: the first min(warmup + steps, --input-rotations) rotations of every stream (43 by
+default: 43 m of travel, inside the scene's wall ring); longer runs feed them again cyclically. A batch is exactly one rotation, so
+the columns continue seamlessly across a wrap; only the pose steps back to the start of the drive there. Memory and set-up time stay
+bounded whatever --steps is. value = published range-image cells per second (NaN cells
 included) over all GPUs, in Mpoints/s. Streams never interact, so ranks share nothing on the data path
 (weak scaling: 256 streams per GPU); the only collective is the gather of per-rank result counts at the end
 (RCCL when launched under torch.distributed.run, also at world size 1: `rccl_world` in the JSON line).
 
-The JSON line also carries
+A plain run does only what the headline needs: it generates the inputs, warms up, times K steps once, writes the outputs of the
+last step if --dump-outputs is given and prints the line (value, ms_per_step, the kernel times and roofline of that same timed region).
+--dump-outputs DIR writes what a caller of the timed path receives after its last step, as float32 / float64 .npy files: the stream state
+of every stream (state.npy) and, for a fixed seeded sample of streams, every field of the newest published rotation (columns_<field>.npy,
+columns_meta.npy: stream, first and last global column). All values are finite: the NaN of a cell without a return is written as 0 and
+columns_<field>_class.npy marks it (0 finite, 1 NaN, 2 +inf, 3 -inf). The inputs depend only on the arguments, so two builds compare output for output.
+
+With --full the line also carries (the headline leg then runs --repeats times, 3 by default, and the full record goes to a file)
   roofline          dominant kernel vs the 8 TB/s HBM roof: algorithmic bytes per launch (19.5 B per cell at 64 rows,
                     SURVEY 8d) / its average duration measured with HIP events on the engine's stream
   verified_streams  after the timed region (outside it) the whole input of a few of the 256 streams is replayed through the
@@ -47,13 +57,24 @@ STATE_FIELDS = ("reset_required", "ring_buffer_start_global_column_index", "ring
 
 MIRROR_ONLY_FIELDS = ("number_of_visited_neighbors", "finished_at_continuous_azimuth_angle", "tree_num_points", "cluster_width")
 
+# distinct input rotations per stream a leg generates (--input-rotations); batch b of a leg is input rotation b mod this
+INPUT_ROTATIONS = 43
+
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=80)  # (a timed region fills and drains a three-deep pipeline once: 40 steps read 5 % low)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=3, help="repeats of the headline leg inside one run: the line carries the median and the spread")
+    ap.add_argument("--full", action="store_true",
+                    help="also the report legs (oracle check, S128, strong split, fewer streams, latency, host-fed, vegetation, CPU baseline, replay, "
+                         "real data) and the headline repeats; without it a plain run times the headline leg once")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the timed path computed in its last step (stream states, a seeded sample of published columns) as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="repeats of the headline leg inside one run: the line carries the median and the spread (default 3 with --full, else 1)")
+    ap.add_argument("--input-rotations", type=int, default=INPUT_ROTATIONS,
+                    help="distinct rotations generated per stream; a leg with more batches feeds them again cyclically (bounds memory and set-up time)")
     ap.add_argument("--streams", type=int, default=256, help="sensor streams per GPU")
     ap.add_argument("--firings", type=int, default=2200, help="firings per stream per step (2200 = one rotation)")
     ap.add_argument("--sensor", default="s64", choices=["s64", "s128"])
@@ -77,7 +98,10 @@ def parse():
     ap.add_argument("--stub-engine", action="store_true",
                     help="TEST ONLY (tests/test_bench_launcher.py): tests/bench_stub.py instead of the HIP engine, gloo on CPU; exercises the launcher and the "
                          "aggregation over ranks, the line says data = 'stub' and is not a measurement")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    return args
 
 
 def pin_to_gpu_numa_node(torch, dev_index):
@@ -152,17 +176,19 @@ def _bits_equal(a, b):
     return np.array_equal(a, b)
 
 
-def verify_against_oracle(eng, cfg, R, xyz, inten, poses, which, tail_cols=1500):
-    """Replay the complete input of the streams `which` through the CPU oracle and require the engine's stream state and the last
+def verify_against_oracle(eng, cfg, R, xyz, inten, poses, which, tail_cols=1500, n_batches=None):
+    """Replay the complete input of the streams `which` (the `n_batches` batches as fed: input rotation b mod len(xyz)) through the CPU oracle and require the engine's stream state and the last
     `tail_cols` published columns (every field of the column view: geometry bit patterns, labels, ignore flags, tree roots, raw
     cluster ids) to be equal. Raises SystemExit on any difference: a fast run with different results is not a result."""
     from oracle.pyoracle import Oracle
-    nb, _, F = xyz.shape[0], xyz.shape[1], xyz.shape[2]
+    n_in, F = xyz.shape[0], xyz.shape[2]
+    nb = n_in if n_batches is None else n_batches
+    order = [b % n_in for b in range(nb)]
     t0 = time.perf_counter()
     for s in which:
-        hx = xyz[:, s].reshape(nb * F, R, 3).cpu().numpy()
-        hi = inten[:, s].reshape(nb * F, R).cpu().numpy()
-        hp = poses[:, s].reshape(nb * F, 12).cpu().numpy()
+        hx = xyz[:, s].cpu().numpy()[order].reshape(nb * F, R, 3)
+        hi = inten[:, s].cpu().numpy()[order].reshape(nb * F, R)
+        hp = poses[:, s].cpu().numpy()[order].reshape(nb * F, 12)
         o = Oracle(cfg, R, record=True)
         o.keep_published_tail(tail_cols + 256)
         rc = o.add_firings(hx, hi, hp)
@@ -390,7 +416,8 @@ def run_throughput(ctx, sensor, cfg, seeds, F, steps, warmup, n_verify, inputs=N
     torch, dist = ctx.torch, ctx.dist
     R, S = sensor.num_rows, len(seeds)
     n_batches = warmup + steps
-    xyz, inten, poses = inputs if inputs is not None else gen_inputs(torch, ctx.dev, sensor, seeds, F, n_batches)
+    xyz, inten, poses = inputs if inputs is not None else gen_inputs(torch, ctx.dev, sensor, seeds, F, min(n_batches, INPUT_ROTATIONS))
+    n_in = int(xyz.shape[0])  # batch b is input rotation b mod n_in
     ctx.device_sync()
     eng = ctx.engine(cfg, R, S)
     eng.record_events(False)
@@ -399,7 +426,7 @@ def run_throughput(ctx, sensor, cfg, seeds, F, steps, warmup, n_verify, inputs=N
         eng.set_option(name, val)
 
     for b in range(warmup):
-        eng.add_firings_device(F, xyz[b], inten[b], poses[b])
+        eng.add_firings_device(F, xyz[b % n_in], inten[b % n_in], poses[b % n_in])
     rc = eng.sync()
     if rc != 0:
         raise SystemExit(f"engine error {rc}: {eng.last_error()}")
@@ -414,7 +441,7 @@ def run_throughput(ctx, sensor, cfg, seeds, F, steps, warmup, n_verify, inputs=N
     ctx.barrier()
     t0 = time.perf_counter()
     for b in range(warmup, n_batches):
-        eng.add_firings_device(F, xyz[b], inten[b], poses[b])
+        eng.add_firings_device(F, xyz[b % n_in], inten[b % n_in], poses[b % n_in])
     rc = eng.sync()
     ctx.device_sync()
     own_elapsed = time.perf_counter() - t0
@@ -445,7 +472,7 @@ def run_throughput(ctx, sensor, cfg, seeds, F, steps, warmup, n_verify, inputs=N
     verified = None
     if n_verify > 0:
         which = sorted({(k * (S - 1)) // max(1, n_verify - 1) for k in range(n_verify)}) if n_verify > 1 else [0]
-        verified = verify_against_oracle(eng, cfg, R, xyz, inten, poses, which)
+        verified = verify_against_oracle(eng, cfg, R, xyz, inten, poses, which, n_batches=n_batches)
 
     alg_bytes_per_cell = 18.0 + 96.0 / R  # 13 B read + 5 B written per cell + 96 B pose per column
     batches = max(1, ktimes["batches"])  # kernel launches of each kind: the engine may cut a step into pipelined sub-batches
@@ -868,9 +895,81 @@ def host_fed_report(ctx, sensor, cfg, F, xyz, inten, poses, steps=6):
                     "current batch's kernels) and handed to cc_engine_add_firings_device: the PCIe-inclusive rate of the headline workload"}
 
 
+DUMP_BUDGET_BYTES = 56 << 20  # all files of --dump-outputs together (the limit is 64 MB)
+DUMP_MAX_STREAMS = 8
+
+
+def dump_class(a):
+    """float32 per element: 0 finite, 1 NaN, 2 +inf, 3 -inf."""
+    c = np.zeros(a.shape, dtype=np.float32)
+    c[np.isnan(a)] = 1
+    c[np.isposinf(a)] = 2
+    c[np.isneginf(a)] = 3
+    return c
+
+
+def dump_outputs(eng, R, F, out_dir, seed=20261016):
+    """What a caller of the timed path receives after its last step, as .npy files in `out_dir` (float32 where the field fits, else float64):
+    state.npy — [streams][STATE_FIELDS] of every stream; columns_<field>.npy — [k][columns][rows], the newest F published columns (the last
+    step's rotation) of k streams drawn with a fixed seed (as many as the byte budget allows, at most DUMP_MAX_STREAMS);
+    columns_meta.npy — [k][3]: stream, first and last global column. Fields that the throughput mode does not produce are left out.
+    Every value written is finite: a floating field's NaN / inf (a cell without a return) is written as 0 in columns_<field>.npy, and
+    columns_<field>_class.npy says what stood there (dump_class: 0 finite, 1 NaN, 2 +inf, 3 -inf)."""
+    from continuous_clustering_amd import capi
+    os.makedirs(out_dir, exist_ok=True)
+    S = eng.num_streams
+    states = [eng.state(s) for s in range(S)]
+    np.save(os.path.join(out_dir, "state.npy"), np.array([[float(st[k]) for k in STATE_FIELDS] for st in states], dtype=np.float64))
+    fields = [f for f in capi.COLUMN_FIELDS if f not in MIRROR_ONLY_FIELDS]
+    as_type = {f: (np.float32 if np.dtype(capi.COLUMN_FIELDS[f]) == np.float32 or np.dtype(capi.COLUMN_FIELDS[f]).itemsize == 1 else np.float64)
+               for f in fields}  # (exact: bytes and float32 as float32, every wider integer and float64 as float64)
+    floating = [f for f in fields if np.dtype(capi.COLUMN_FIELDS[f]).kind == "f"]
+    per_stream = F * R * (sum(np.dtype(t).itemsize for t in as_type.values()) + 4 * len(floating))
+    k = max(1, min(S, DUMP_MAX_STREAMS, DUMP_BUDGET_BYTES // per_stream))
+    which = sorted(int(s) for s in np.random.default_rng(seed).choice(S, size=k, replace=False))
+    hi = [states[s]["first_unpublished_global_column_index"] - 1 for s in which]
+    n_cols = min([F] + [h - states[s]["ring_buffer_start_global_column_index"] + 1 for s, h in zip(which, hi)])
+    if n_cols <= 0:
+        raise SystemExit("dump: no published columns to write")
+    cols = {f: np.empty((k, n_cols, R), dtype=as_type[f]) for f in fields}
+    for j, (s, h) in enumerate(zip(which, hi)):
+        got = eng.read_columns(h - n_cols + 1, h, stream=s, fields=fields)
+        for f in fields:
+            cols[f][j] = got[f]
+    for f in fields:
+        if f in floating:
+            np.save(os.path.join(out_dir, f"columns_{f}_class.npy"), dump_class(cols[f]))
+            cols[f][~np.isfinite(cols[f])] = 0
+        np.save(os.path.join(out_dir, f"columns_{f}.npy"), cols[f])
+    np.save(os.path.join(out_dir, "columns_meta.npy"), np.array([[s, h - n_cols + 1, h] for s, h in zip(which, hi)], dtype=np.float64))
+
+
+def slim_roofline(o):
+    rf = dict(o.get("roofline") or {})
+    for k in ("rocprof_source", "traffic_source", "dominant_by", "note"):
+        rf.pop(k, None)
+    if isinstance(rf.get("valu"), dict):
+        rf["valu"] = {k: v for k, v in rf["valu"].items() if k in ("achieved", "peak", "unit", "frac", "frac_4clk", "roof_source")}
+    return rf
+
+
+def headline_line(o):
+    """The line of a plain run: the contract's keys and what the one timed region measured."""
+    line = {k: o.get(k) for k in ("metric", "value", "value_min", "value_max", "value_repeats", "value_is", "unit", "n_gpus", "steps", "warmup",
+                                  "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "cells_published",
+                                  "clusters_finished", "serial_columns", "association", "kernel_ms_per_step", "rccl_world", "numa_pin",
+                                  "per_rank_value", "per_rank")}
+    line["roofline"] = slim_roofline(o)
+    return {k: (v if not isinstance(v, (dict, list)) else _r(v)) for k, v in line.items()}
+
+
 def main():
+    global INPUT_ROTATIONS
     args = parse()
     maybe_spawn(args)
+    if args.input_rotations < 1:
+        raise SystemExit("--input-rotations must be at least 1")
+    INPUT_ROTATIONS = args.input_rotations
     import torch
     import torch.distributed as dist
     from continuous_clustering_amd import capi, synth
@@ -909,7 +1008,9 @@ def main():
     sensor = synth.SensorModel.s64() if args.sensor == "s64" else synth.SensorModel.s128()
     cfg = capi.Config.kitti() if args.sensor == "s64" else capi.Config.vls128()
     S, F, R = args.streams, args.firings, sensor.num_rows
-    n_verify = 0 if (args.no_verify or stub) else (args.verify_streams if rank == 0 else 0)
+    n_verify = 0 if (args.no_verify or stub or not args.full) else (args.verify_streams if rank == 0 else 0)
+    if args.dump_outputs and stub:
+        raise SystemExit("--dump-outputs needs the HIP engine (the stub computes nothing)")
 
     # ================= legs every rank takes part in =================
     # ---- headline: weak scaling, S streams per GPU (BASELINE.json configs[2] per GPU) ----
@@ -963,7 +1064,18 @@ def main():
             "per_rank_value": [r["value"] for r in res["per_rank"]],
             "per_rank": res["per_rank"],
         }
+        if args.dump_outputs:
+            dump_outputs(eng, R, F, args.dump_outputs)
     eng.close()
+
+    # ---- a plain run ends here: everything below is a report beside the headline (--full) ----
+    if not args.full:
+        ctx.barrier()
+        if use_dist:
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(headline_line(out)), flush=True)
+        return
 
     # ---- strong split (north_star: "256 concurrent streams" sharded across the GPUs of one node): --total-streams streams in all,
     #      stream s on rank s mod N; the same step, fewer streams per GPU as N grows ----
@@ -1124,12 +1236,7 @@ def slim_line(o):
                                   "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
     cfgd = dict(o.get("config") or {})
     line["config"] = cfgd
-    rf = dict(o.get("roofline") or {})
-    for k in ("rocprof_source", "traffic_source", "dominant_by", "note"):
-        rf.pop(k, None)
-    if isinstance(rf.get("valu"), dict):
-        rf["valu"] = {k: v for k, v in rf["valu"].items() if k in ("achieved", "peak", "unit", "frac", "frac_4clk", "roof_source")}
-    line["roofline"] = rf
+    line["roofline"] = slim_roofline(o)
     cb = o.get("cpu_baseline")
     if cb:
         line["cpu_baseline"] = {"value": cb.get("value"), "unit": cb.get("unit"), "cores": cb.get("cores"), "kind": cb.get("kind"),

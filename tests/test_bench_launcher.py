@@ -10,13 +10,14 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(*extra, env_extra=None):
+def run_bench(*extra, env_extra=None, full=True):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     env.update(env_extra or {})
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub-engine", "--streams", "3", "--firings", "40", "--steps", "4",
-                        "--warmup", "1", "--no-s128", *extra], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--warmup", "1", "--no-s128", *(["--full"] if full else []), *extra], capture_output=True, text=True, timeout=600, env=env,
+                       cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -61,9 +62,29 @@ def test_under_a_launcher_the_world_is_the_launchers():
     s.close()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub-engine", "--streams", "2", "--firings", "30",
-                        "--steps", "2", "--warmup", "1", "--no-s128", "--no-strong-split"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--steps", "2", "--warmup", "1", "--no-s128", "--no-strong-split", "--full"], capture_output=True, text=True, timeout=600, env=env,
+                       cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["cells_published"] == 2 * 2 * 30 * 64 * 2 and "strong_split" not in out
+
+
+def test_plain_run_times_the_headline_leg_once():
+    """Without --full: --steps timed steps of the headline leg, one repeat, no report legs; the line keeps the contract's keys."""
+    out = run_bench("--gpus", "1", "--total-streams", "5", full=False)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 4 and out["warmup"] == 1 and len(out["value_repeats"]) == 1
+    assert out["cells_published"] == 3 * 40 * 64 * 4  # exactly --steps steps were timed
+    assert abs(out["value"] - out["cells_published"] / (out["ms_per_step"] * 4 / 1e3) / 1e6) < 1e-6 * out["value"] + 1e-9
+    for k in ("strong_split", "s128", "cpu_baseline", "few_streams", "cluttered", "replay", "semantic_kitti", "detail"):
+        assert k not in out, k
+    assert out["n_gpus"] == 1 and out["rccl_world"] == 0
+
+
+def test_steps_beyond_the_generated_rotations_are_fed_cyclically():
+    """More batches than --input-rotations: the inputs are fed again cyclically and exactly --steps steps are still timed."""
+    out = run_bench("--gpus", "1", "--input-rotations", "2", full=False)
+    assert out["steps"] == 4 and out["cells_published"] == 3 * 40 * 64 * 4

@@ -375,7 +375,7 @@ def test_bench_under_the_distributed_launcher_world_1():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29547",
            os.path.join(root, "bench.py"), "--gpus", "1", "--streams", "64", "--steps", "4", "--warmup", "3", "--total-streams", "32", "--no-s128",
-           "--no-cpu-baseline", "--no-latency", "--no-few-streams", "--no-host-fed", "--verify-streams", "2"]
+           "--no-cpu-baseline", "--no-latency", "--no-few-streams", "--no-host-fed", "--verify-streams", "2", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", CC_BENCH_PIN="1")
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]

@@ -11,7 +11,7 @@ import sys, os
 sys.path.insert(0, %r)
 import continuous_clustering_amd as cca
 cca.LIB_PATH = os.path.join(os.path.dirname(cca.LIB_PATH), %%r)
-sys.argv = ['bench.py', '--steps', %r, '--warmup', '3', '--no-cpu-baseline', '--no-latency']
+sys.argv = ['bench.py', '--full', '--steps', %r, '--warmup', '3', '--no-cpu-baseline', '--no-latency']
 import bench
 bench.main()
 """ % (ROOT, steps)

@@ -6,7 +6,7 @@ import sys, os
 sys.path.insert(0, %r)
 import continuous_clustering_amd as cca
 cca.LIB_PATH = os.path.join(os.path.dirname(cca.LIB_PATH), %%r)
-sys.argv = ['bench.py', '--sensor', 's128', '--firings', '1700', '--steps', '10', '--warmup', '3', '--no-cpu-baseline', '--no-latency', '--no-s128', '--no-verify']
+sys.argv = ['bench.py', '--full', '--sensor', 's128', '--firings', '1700', '--steps', '10', '--warmup', '3', '--no-cpu-baseline', '--no-latency', '--no-s128', '--no-verify']
 import bench
 bench.main()
 """ % ROOT

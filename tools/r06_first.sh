@@ -4,10 +4,10 @@ repo=${GRAFT_REPO_ROOT:-/root/repo}
 out=$repo/gpurun_out/r06a
 mkdir -p $out
 cd $repo
-python bench.py --steps 20 --warmup 3 > $out/bench_line.json 2> $out/bench.err
+python bench.py --full --steps 20 --warmup 3 > $out/bench_line.json 2> $out/bench.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_r06a
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_r06a -o bench -- python $repo/bench.py --steps 40 --warmup 3 --no-cpu-baseline --no-latency --no-s128 --no-few-streams --no-host-fed --no-verify > /tmp/prof_r06a.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_r06a -o bench -- python $repo/bench.py --full --steps 40 --warmup 3 --no-cpu-baseline --no-latency --no-s128 --no-few-streams --no-host-fed --no-verify > /tmp/prof_r06a.log 2>&1
 grep '^{' /tmp/prof_r06a.log > $out/prof_bench_line.json
 f=$(find /tmp/prof_r06a -name "*kernel_trace.csv" | head -1)
 python $repo/tools/timeline.py $f 120 > $out/timeline.txt

@@ -4,7 +4,7 @@ repo=${GRAFT_REPO_ROOT:-/root/repo}
 out=$repo/gpurun_out/round_r06g
 mkdir -p $out
 cd $repo
-python bench.py --steps 20 --warmup 3 > $out/bench_line.json 2> $out/bench.err
+python bench.py --full --steps 20 --warmup 3 > $out/bench_line.json 2> $out/bench.err
 cp $repo/gpurun_out/bench_detail.json $out/bench_detail.json 2>/dev/null
 tools/prof.sh r06g --steps 40 --warmup 3 --repeats 1 --no-cpu-baseline --no-latency --no-s128 --no-few-streams --no-host-fed --no-cluttered > $out/prof.log 2>&1
 tools/pmc_sq.sh r06g "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" > $out/sq.log 2>&1

@@ -7,7 +7,7 @@ out=$repo/gpurun_out/r06q; mkdir -p $out; : > $out/sq_bench256.txt
 i=0
 for ctrs in "SQ_WAVES SQ_BUSY_CU_CYCLES SQ_WAIT_ANY" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU" "SQ_LEVEL_WAVES SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE"; do
   i=$((i+1)); rm -rf /tmp/sqb_$i
-  rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d /tmp/sqb_$i -o pmc -- python $repo/bench.py --steps 3 --warmup 2 --repeats 1 --no-cpu-baseline --no-latency --no-s128 --no-few-streams --no-host-fed --no-verify --no-cluttered > /tmp/sqb_$i.log 2>&1
+  rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d /tmp/sqb_$i -o pmc -- python $repo/bench.py --full --steps 3 --warmup 2 --repeats 1 --no-cpu-baseline --no-latency --no-s128 --no-few-streams --no-host-fed --no-verify --no-cluttered > /tmp/sqb_$i.log 2>&1
   f=$(find /tmp/sqb_$i -name "*counter_collection.csv" | head -1)
   [ -z "$f" ] && { echo "pass $i: no output" >> $out/sq_bench256.txt; continue; }
   python - "$f" >> $out/sq_bench256.txt <<'PY'
