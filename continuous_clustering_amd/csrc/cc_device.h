@@ -217,7 +217,7 @@ struct Geometry
     float max_distance_squared;
     int32_t record_events;
     int32_t limit_columns;   // a launch stops consuming firings of a stream once it emitted this many columns
-    int32_t debug_flags;     // experiment switches (cc_engine_set_option "debug_flags"); 0 in production
+    int32_t sl_cap;          // records of a stream's long-scan list the packed window scan may use (<= SL_CAP; option "scan_long_records": tests shrink it)
     int32_t lds_tree_limit;  // unfinished trees kept in LDS before a stream falls back to the global-memory kernel (<= TREE_SLOTS)
     int32_t mirror_fields;   // also produce the per-point fields only the host mirror of range_image_ shows (visited-neighbour counts, the
                              // parent of live-replayed points, per-tree values of finished trees, the tree-link log)
@@ -226,7 +226,6 @@ struct Geometry
     int32_t scan_cap;        // visits a lane of the packed window scan spends on its point before it hands it to the long-scan list (option "scan_cap")
     int32_t scan_stores_fin; // per LAUNCH (cc_engine.hip sets it in the copy it hands to a batch's window scan and serial association kernels, 0 elsewhere):
                              // 1 = the scan writes Planes::sc_fin and the serial kernels read it, 0 = nobody writes it and they recompute (cell_fin)
-    int32_t sl_cap;          // records of a stream's long-scan list the packed window scan may use (<= SL_CAP; option "scan_long_records": tests shrink it)
 };
 
 } // namespace ccd

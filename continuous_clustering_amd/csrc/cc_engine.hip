@@ -54,18 +54,14 @@ struct cc_engine
     bool fuse_front{true};     // option "fuse_front": k_insert_par also does the per-cell part of the segmentation of the columns it fills
     int* h_par_left{nullptr};  // pinned
     int insert_split_blocks{0};      // option "insert_split_blocks": blocks per stream of k_insert_par in such launches (0 = 8 up to 24 streams, 6 up to 32, 4 up to 40, 3 up to 64, else 2; 1 = one)
-    int insert_narrow_blocks{0};     // option "insert_narrow_blocks": above insert_wide_max_streams, blocks of 4 wavefronts, this many per stream (0 = one block of 8)
     int insert_wide_max_streams{160}; // option "insert_wide_max_streams": launches of at most this many streams run k_insert_par with 16 wavefronts
     bool skip_idle_fallbacks{true}; // option "skip_idle_fallbacks": wait for k_insert_par and launch the other insertion kernels only if needed
     hipStream_t stream{nullptr};  // insertion chain (and everything else when not pipelined)
     hipStream_t stream2{nullptr}; // table / segmentation / window-scan chain of the pipelined throughput path
     hipStream_t stream3{nullptr}; // association / publish chain of the pipelined throughput path
     hipStream_t stream4{nullptr}; // window-scan stage of the four-stage pipeline (option "pipeline" = 2)
-    hipStream_t stream7{nullptr}; // k_table with table_on_insert_chain = 2
     hipStream_t stream6{nullptr}; // k_publish of a pipelined batch: off the association chain, which is the longest of the three
     hipEvent_t ev_pubrdy[4]{};
-    hipEvent_t ev_ego[4]{};       // k_ego of the slot's batch on the preparation stream (option "ego_off_chain")
-    bool ego_off_chain{false};    // (measured, round 6: 32 streams - 8 % in the 20-step leg and - 12 % steady with it on — the cross-stream event costs more than the kernel's ~10 us on the chain —, 256 streams + 0)
     hipStream_t stream5{nullptr}; // k_prep of the *next* batch: independent of the engine state, so it runs ahead of the insertion chain
     hipEvent_t ev_ins[4]{}, ev_seg[4]{}, ev_assoc[4]{}, ev_segscan[4]{}, ev_prep[4]{};
     hipEvent_t ev_input{};            // option "input_on_engine_stream": recorded on `stream` when a device call arrives
@@ -104,15 +100,10 @@ struct cc_engine
     unsigned long long* h_input_sum{nullptr};
     bool pipelined{false};        // last submitted batch used all three streams
     bool allow_pipeline{true};    // option "pipeline"
-    bool publish_off_chain{true}; // option "publish_off_chain"
-    int table_on_insert_chain{1}; // option "table_on_insert_chain": k_table 0 = in front of the segmentation chain, 1 = at the end of the insertion chain,
-                                  // 2 = on a (high-priority) stream of its own between the two
-    bool ego_on_insert_chain{false};  // option "ego_on_insert_chain": k_ego (needs the caller's poses only) behind k_table instead of in front of k_seg_pre
     // CC_HOST_PROF=1: where the host's time goes inside a pipelined call (seconds, summed; printed by cc_engine_destroy)
     bool host_prof{false};
     double hp_pre{0}, hp_gate{0}, hp_post{0}, hp_entry{0};
     long long hp_calls{0};
-    bool debug_no_assoc_fallback{false}; // option "debug_no_assoc_fallback": timing experiments only (results are wrong wherever k_assocb stops)
     bool parallel_insert_multi{true}; // option "parallel_insert" = 1: k_insert_multi behind / instead of k_insert_par; 2: k_insert_par only
     bool parallel_insert{true};   // option "parallel_insert": k_insert_par takes the single-column-firing head of every batch
     // low-latency path of cc_engine_add_firings for small calls: one captured hipGraph per (stream, n), pinned staging
@@ -178,12 +169,7 @@ struct cc_engine
     int lazy_clean{0};                                   // batches in the steady shape seen by the plain gate since lazy_ok went off (eight re-arm it)
     uint64_t lazy_batches{0}, lazy_redone{0};            // cc_engine_gate_counters: insertions enqueued ahead of the previous batch's counters / launched a second time
     hipEvent_t ev_gate[4]{};
-    int num_cus{256};                                    // compute units of the device
-    int insert_lds_pad_kb{0};                            // option "insert_lds_pad" (experiment, default 0): launches of at most one block per compute unit ask for this much unused LDS per insertion
-                                                         // block, so that no two of them share a CU. Measured with 81 KB at 256 streams: - 3.5 % (128 rows), - 6 % (64 rows): the blocks of the
-                                                         // other chains' kernels lose the room, and the block times of k_insert_multi did not get shorter (the spread was not CU sharing)
     int defer_tail_max_streams{96};                      // option "defer_tail_max_streams": launches of at most this many streams defer them (0: never)
-    bool streams_pooled{false};                          // the seven streams come from (and return to) the process-wide set cache
     bool slab_planning{false};                           // alloc_plane only records (field, offset): allocate() makes ONE hipMalloc of the total
     size_t slab_bytes{0};
     std::vector<std::pair<void**, size_t>> slab_plan;
@@ -599,13 +585,6 @@ static bool lazy_eligible(const cc_engine* e, int count, int64_t n, bool pipelin
            !e->input_on_engine_stream && e->pipeline_depth >= 1;
 }
 
-// unused dynamic LDS that keeps a second block of the same kernel off the compute unit (see insert_lds_pad_kb)
-static unsigned insert_lds_pad(const cc_engine* e, int blocks, size_t static_bytes)
-{
-    const size_t want = (size_t) e->insert_lds_pad_kb * 1024;
-    return (e->insert_lds_pad_kb > 0 && blocks <= e->num_cus && want > static_bytes) ? (unsigned) (want - static_bytes) : 0u;
-}
-
 static bool use_small_front(const cc_engine* e, int count, int64_t n, bool pipeline)
 {
     return e->small_front && !pipeline && count == 1 && n <= e->seg_small_max && n < 64 && e->g.num_rows <= WAVE;
@@ -765,22 +744,13 @@ int launch_batch(cc_engine* e, int first_stream, int count, int64_t n, const flo
         {
             if (fuse)
             {
-                // the fused insertion needs the per-firing ego records: they only depend on the caller's poses (and the robot transform, which the
-                // host writes between batches) — so not on the insertion chain, which is what a step waits for: on the preparation stream (idle while the
-                // block-parallel insertion takes the batches), where they run beside the PREVIOUS batch's insertion; the insertion waits for the
-                // event. The records' buffer belongs to the batch-descriptor slot: its last readers (segmentation chain of four batches ago) are
-                // in front of that slot's publishing event.
-                const bool off = e->ego_off_chain && si != sb && !e->capturing;
-                hipStream_t se = off ? e->stream5 : si;
-                if (off)
-                    CC_HIP_CHECK(e, hipStreamWaitEvent(se, e->ev_assoc[slot], 0));
-                hipLaunchKernelGGL(cck::k_ego, dim3((unsigned) ((n + 255) / 256), (unsigned) count), dim3(256), 0, se, (const StreamState*) e->d_states, first_stream,
+                // the fused insertion needs the per-firing ego records (they only depend on the caller's poses and the robot transform, which the
+                // host writes between batches): k_ego runs in front of it on the insertion chain. (On the preparation stream, beside the previous
+                // batch's insertion, it measured slower: the cross-stream event costs more than the kernel's ~10 us on the chain.) The records'
+                // buffer belongs to the batch-descriptor slot: its last readers (segmentation chain of four batches ago) are in front of that
+                // slot's publishing event.
+                hipLaunchKernelGGL(cck::k_ego, dim3((unsigned) ((n + 255) / 256), (unsigned) count), dim3(256), 0, si, (const StreamState*) e->d_states, first_stream,
                                    e->cfg, d_pose, (long long) n, cur_ntotal, cur_f0, d_ego);
-                if (off)
-                {
-                    CC_HIP_CHECK(e, hipEventRecord(e->ev_ego[slot], se));
-                    CC_HIP_CHECK(e, hipStreamWaitEvent(si, e->ev_ego[slot], 0));
-                }
             }
             if (gate && !gate_zeroed)
                 CC_HIP_CHECK(e, hipMemsetAsync(left, 0, 2 * sizeof(int), si));
@@ -797,23 +767,14 @@ int launch_batch(cc_engine* e, int first_stream, int count, int64_t n, const flo
                 // 40 streams: 5 blocks - 3 .. - 5 % against 4 (the rule is not exact: measured points decide)
                 const int nb = e->insert_split_blocks > 0 ? e->insert_split_blocks
                                                           : (count <= 24 ? 8 : (count <= 32 ? 6 : (count <= 40 ? 4 : (count <= 64 ? 3 : (count <= 96 ? 2 : 1)))));
-                hipLaunchKernelGGL((cck::k_insert_par<1, 2 * cck::IP_WAVES>), dim3(count, nb), dim3(128 * cck::IP_WAVES), insert_lds_pad(e, count * nb, 20 * 1024), si, g, e->cfg, Pt, e->d_states,
+                hipLaunchKernelGGL((cck::k_insert_par<1, 2 * cck::IP_WAVES>), dim3(count, nb), dim3(128 * cck::IP_WAVES), 0, si, g, e->cfg, Pt, e->d_states,
                                    first_stream, d_xyz, d_int, d_pose, (long long) n, cur_ntotal, cur_f0, slot, left, ego_in, prev_left);
                 if (nb > 1)
                     hipLaunchKernelGGL(cck::k_insert_par_fin<1>, dim3(count), dim3(256), 0, si, g, Pt, e->d_states, first_stream, d_xyz, (long long) n,
                                        cur_ntotal, cur_f0, slot, left, fuse ? 1 : 0, prev_left);
             }
-            else if (e->insert_narrow_blocks > 0)
-            {
-                // (experiment: small blocks find room on a busy CU sooner than one block of 8 wavefronts)
-                hipLaunchKernelGGL((cck::k_insert_par<1, 4>), dim3(count, e->insert_narrow_blocks), dim3(256), 0, si, g, e->cfg, Pt, e->d_states,
-                                   first_stream, d_xyz, d_int, d_pose, (long long) n, cur_ntotal, cur_f0, slot, left, ego_in, prev_left);
-                if (e->insert_narrow_blocks > 1)
-                    hipLaunchKernelGGL(cck::k_insert_par_fin<1>, dim3(count), dim3(256), 0, si, g, Pt, e->d_states, first_stream, d_xyz, (long long) n,
-                                       cur_ntotal, cur_f0, slot, left, fuse ? 1 : 0, prev_left);
-            }
             else
-                hipLaunchKernelGGL((cck::k_insert_par<1, cck::IP_WAVES>), dim3(count), dim3(64 * cck::IP_WAVES), insert_lds_pad(e, count, 20 * 1024), si, g, e->cfg, Pt, e->d_states,
+                hipLaunchKernelGGL((cck::k_insert_par<1, cck::IP_WAVES>), dim3(count), dim3(64 * cck::IP_WAVES), 0, si, g, e->cfg, Pt, e->d_states,
                                    first_stream, d_xyz, d_int, d_pose, (long long) n, cur_ntotal, cur_f0, slot, left, ego_in, prev_left);
             if (gate)
             {
@@ -962,7 +923,7 @@ int launch_batch(cc_engine* e, int first_stream, int count, int64_t n, const flo
             // the whole call in one launch where the results go to pinned memory (the captured graph of cc_engine_add_firings' small calls): the
             // serial fall-backs, needed once in a long while, are launched by the host when the kernel asks for them (add_firings_small)
             const bool small_all = e->small_all && e->capture_mirror.state != nullptr && e->capture_mirror.tail_req != nullptr && e->assoc_batch &&
-                                   e->assoc_waves >= 2 && rpl == 1 && e->cfg.cluster_point_trees_every_nth_column == 1 && !e->debug_no_assoc_fallback;
+                                   e->assoc_waves >= 2 && rpl == 1 && e->cfg.cluster_point_trees_every_nth_column == 1;
             if (small_all)
             {
                 hipLaunchKernelGGL(cck::k_small_all, dim3(1), dim3(cck::AB_THREADS), cck::insert2_lds_bytes(g.num_rows), si, g, e->cfg, Pf, e->d_states, first_stream,
@@ -1011,31 +972,19 @@ int launch_batch(cc_engine* e, int first_stream, int count, int64_t n, const flo
         if (seg_small)
             need_segpre = false;
         // (with the fused front half k_insert_par reads and writes the running table `curtab` on the insertion chain: k_table of a batch that is not
-        // fused has to run on that chain too, whatever the option says — elsewhere nothing would order it against the next batch's insertion)
-        const int table_opt = (e->fuse_front && rpl == 1) ? 1 : e->table_on_insert_chain; // (above 64 rows nothing is fused: only k_table touches the running table)
-        const bool table_early = si != sb && table_opt != 0;
-        // (a stream of its own: the next batch's insertion does not queue behind it)
-        hipStream_t st_table = (table_early && table_opt == 2 && !e->capturing) ? e->stream7 : si;
+        // fused has to run on that chain too — elsewhere nothing would order it against the next batch's insertion)
+        const bool table_early = si != sb;
         if (table_early && need_segpre)
         {
-            if (st_table != si)
-            {
-                CC_HIP_CHECK(e, hipEventRecord(e->ev_ins[slot], si));
-                CC_HIP_CHECK(e, hipStreamWaitEvent(st_table, e->ev_ins[slot], 0));
-            }
             if (rpl == 1)
-                hipLaunchKernelGGL(cck::k_table<1>, dim3(count), dim3(64 * cck::TABLE_WAVES), 0, st_table, g, Pt, e->d_states, first_stream, slot);
+                hipLaunchKernelGGL(cck::k_table<1>, dim3(count), dim3(64 * cck::TABLE_WAVES), 0, si, g, Pt, e->d_states, first_stream, slot);
             else
-                hipLaunchKernelGGL(cck::k_table<2>, dim3(count), dim3(64 * cck::TABLE_WAVES), 0, st_table, g, Pt, e->d_states, first_stream, slot);
+                hipLaunchKernelGGL(cck::k_table<2>, dim3(count), dim3(64 * cck::TABLE_WAVES), 0, si, g, Pt, e->d_states, first_stream, slot);
         }
-        const bool ego_early = table_early && e->ego_on_insert_chain;
-        if (ego_early && !ego_done && need_segpre)
-            hipLaunchKernelGGL(cck::k_ego, dim3((unsigned) ((n + 255) / 256), (unsigned) count), dim3(256), 0, st_table, (const StreamState*) e->d_states, first_stream,
-                               e->cfg, d_pose, (long long) n, (long long) e->cur_ntotal, (long long) e->cur_f0, d_ego);
         if (si != sb)
         {
             if (!pre_done)
-                CC_HIP_CHECK(e, hipEventRecord(e->ev_ins[slot], st_table));
+                CC_HIP_CHECK(e, hipEventRecord(e->ev_ins[slot], si));
             CC_HIP_CHECK(e, hipStreamWaitEvent(sb, e->ev_ins[slot], 0));
         }
         // ---- table + segmentation + window-scan chain ------------------------------------------------------------
@@ -1047,7 +996,7 @@ int launch_batch(cc_engine* e, int first_stream, int count, int64_t n, const flo
             else
                 hipLaunchKernelGGL(cck::k_table<2>, dim3(count), dim3(64 * cck::TABLE_WAVES), 0, sb, g, Pt, e->d_states, first_stream, slot);
         }
-        if (!ego_early && !ego_done && need_segpre)
+        if (!ego_done && need_segpre)
             hipLaunchKernelGGL(cck::k_ego, dim3((unsigned) ((n + 255) / 256), (unsigned) count), dim3(256), 0, sb, (const StreamState*) e->d_states, first_stream,
                            e->cfg, d_pose, (long long) n, (long long) e->cur_ntotal, (long long) e->cur_f0, d_ego);
         if (!need_segpre)
@@ -1223,7 +1172,7 @@ int launch_batch(cc_engine* e, int first_stream, int count, int64_t n, const flo
         bool global_done = false; // k_associate's work was done inside the last k_assoc3 launch
         // a lean small call (k_small_front in front, results mirrored): k_assocb, then ONE kernel for the serial fall-backs, the ids and the mirror
         const bool small_tail = small_front && e->capture_mirror.state != nullptr && batch_assoc && e->assoc_waves >= 2 && rpl == 1 &&
-                                e->cfg.cluster_point_trees_every_nth_column == 1 && !e->debug_no_assoc_fallback;
+                                e->cfg.cluster_point_trees_every_nth_column == 1;
         if (small_tail)
         {
             launch_assocb();
@@ -1256,8 +1205,6 @@ int launch_batch(cc_engine* e, int first_stream, int count, int64_t n, const flo
                 // per stream waiting for 45 KB of LDS on a busy CU. One block per stream when it is what associates, or while k_assocb has had to stop
                 // lately (adaptive_rounds > 1), or when the caller pinned the number of rounds
                 const int blocks = (batch_assoc && e->assoc_rounds == 0 && adaptive_rounds == 1 && !e->capturing) ? (count < e->assoc_sweep_blocks ? count : e->assoc_sweep_blocks) : count;
-                if (batch_assoc && e->debug_no_assoc_fallback)
-                    continue;
                 if (rpl == 1)
                     hipLaunchKernelGGL(cck::k_assoc3<1>, dim3(blocks), block, 0, sa, gs, e->cfg, e->P, e->d_states, first_stream, slot, limited, count, 1);
                 else
@@ -1281,7 +1228,7 @@ int launch_batch(cc_engine* e, int first_stream, int count, int64_t n, const flo
         if (!marked7)
             CC_MARK(sa); // ev7: assoc_lds (without the batch-parallel kernel: the serial LDS kernel)
         // streams whose unfinished trees do not fit the LDS pool (or exotic window configs) continue in global memory
-        if ((batch_assoc && e->debug_no_assoc_fallback) || global_done)
+        if (global_done)
             ;
         else if (rpl == 1)
             hipLaunchKernelGGL(cck::k_associate<1>, dim3(count), dim3(64), 0, sa, g, e->cfg, e->P, e->d_states, first_stream, slot);
@@ -1294,7 +1241,7 @@ int launch_batch(cc_engine* e, int first_stream, int count, int64_t n, const flo
         // The ids of the published columns only read what the association of THIS batch left behind (tree root of every cell, cluster id
         // at the root cell; neither is touched again before the ring wraps), so in the pipelined mode they are written on a stream of their
         // own and the next batch's association starts without waiting for them.
-        hipStream_t spub = (si != sa && e->publish_off_chain) ? e->stream6 : sa;
+        hipStream_t spub = si != sa ? e->stream6 : sa;
         if (spub != sa)
         {
             CC_HIP_CHECK(e, hipEventRecord(e->ev_pubrdy[slot], sa));
@@ -1433,7 +1380,6 @@ int sync_all(cc_engine* e)
     CC_HIP_CHECK(e, hipStreamSynchronize(e->stream4));
     CC_HIP_CHECK(e, hipStreamSynchronize(e->stream5));
     CC_HIP_CHECK(e, hipStreamSynchronize(e->stream6));
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream7));
     for (bool& b : e->assoc_pending)
         b = false;
     e->idle = true;
@@ -1803,8 +1749,8 @@ int add_firings_small(cc_engine* e, int stream, int64_t n, const float* xyz, con
 {
     // the whole call as one kernel (k_small_all), launched directly: no graph to capture per call size, any n the small-call kernels take
     const bool direct_ok = e->small_direct && e->small_all && use_small_front(e, 1, n, false) && e->assoc_batch && e->assoc_waves >= 2 &&
-                           e->cfg.cluster_point_trees_every_nth_column == 1 && !e->debug_no_assoc_fallback && n <= SMALL_STAGE;
-    if (!e->allow_graphs || e->timing || (n > SMALL_MAX && !direct_ok) || e->g.debug_flags)
+                           e->cfg.cluster_point_trees_every_nth_column == 1 && n <= SMALL_STAGE;
+    if (!e->allow_graphs || e->timing || (n > SMALL_MAX && !direct_ok))
         return -1;
     const int R = e->g.num_rows;
     const size_t b_xyz = (size_t) SMALL_STAGE * R * 3 * sizeof(float), b_int = (((size_t) SMALL_STAGE * R) + 15) & ~(size_t) 15,
@@ -2149,14 +2095,14 @@ int add_firings_small(cc_engine* e, int stream, int64_t n, const float* xyz, con
 // A HIP stream gets its hardware queue when it is first used, and queues are handed to the compute pipes in creation order. The four chains of
 // the pipelined path only overlap as designed when their queues sit on different pipes: the first engine of a process got that by accident
 // (four queues created back to back), every later engine got recycled queues in another order — insertion and association on one pipe — and
-// ran 10 - 15 % slower at 32 streams, 6 - 10 % at 256 (tools/step_probe.py). So a set of seven streams is created once per
+// ran 10 - 15 % slower at 32 streams, 6 - 10 % at 256 (tools/step_probe.py). So a set of six streams is created once per
 // device, its queues are materialised in a fixed order (one empty launch each: the four chains first), and the set is kept for the next engine
 // when an engine is destroyed. Two engines alive at the same time get two sets.
 __global__ void k_touch_stream() {}
 
 struct StreamSet
 {
-    hipStream_t s[7]{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // stream, stream2 .. stream7
+    hipStream_t s[6]{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // stream, stream2 .. stream6
 };
 std::mutex g_stream_sets_mu;
 std::vector<std::pair<int, StreamSet>> g_stream_sets; // (device, set) not in use by a live engine
@@ -2177,17 +2123,17 @@ bool acquire_stream_set(int device, StreamSet* out)
     (void) hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi); // numerically lower = higher priority
     // The serial chains (insertion, association) bound a pipelined step; the table / segmentation / scan chain between them is
     // throughput work with slack, so it gets the low-priority queue and yields issue slots and memory bandwidth to the other two.
-    const int prio[7] = {prio_hi, prio_lo, prio_hi, prio_lo, prio_lo, prio_lo, prio_hi};
+    const int prio[6] = {prio_hi, prio_lo, prio_hi, prio_lo, prio_lo, prio_lo};
     StreamSet set;
-    for (int i = 0; i < 7; i++)
+    for (int i = 0; i < 6; i++)
         if (hipStreamCreateWithPriority(&set.s[i], hipStreamNonBlocking, prio[i]) != hipSuccess)
         {
             for (int k = 0; k < i; k++)
                 (void) hipStreamDestroy(set.s[k]);
             return false;
         }
-    // queues in this order: insertion, segmentation, association, window scan (the four chains), then publish, table, preparation
-    for (int i : {0, 1, 2, 3, 5, 6, 4})
+    // queues in this order: insertion, segmentation, association, window scan (the four chains), then publish, preparation
+    for (int i : {0, 1, 2, 3, 5, 4})
     {
         hipLaunchKernelGGL(k_touch_stream, dim3(1), dim3(1), 0, set.s[i]);
         (void) hipStreamSynchronize(set.s[i]);
@@ -2202,22 +2148,11 @@ void release_stream_set(int device, const StreamSet& set)
     g_stream_sets.push_back({device, set});
 }
 
-// (all streams idle) the pooled set goes back for the next engine of the process; CU-masked experiment streams are destroyed
+// (all streams idle) the set goes back for the next engine of the process
 void give_back_streams(cc_engine* e)
 {
-    hipStream_t all[7] = {e->stream, e->stream2, e->stream3, e->stream4, e->stream5, e->stream6, e->stream7};
-    if (e->streams_pooled)
-    {
-        StreamSet set;
-        for (int i = 0; i < 7; i++)
-            set.s[i] = all[i];
-        release_stream_set(e->device, set);
-    }
-    else
-        for (hipStream_t st : all)
-            if (st)
-                (void) hipStreamDestroy(st);
-    e->stream = e->stream2 = e->stream3 = e->stream4 = e->stream5 = e->stream6 = e->stream7 = nullptr;
+    release_stream_set(e->device, StreamSet{{e->stream, e->stream2, e->stream3, e->stream4, e->stream5, e->stream6}});
+    e->stream = e->stream2 = e->stream3 = e->stream4 = e->stream5 = e->stream6 = nullptr;
 }
 } // namespace
 
@@ -2288,51 +2223,13 @@ int cc_engine_create(cc_engine** out, int device, int num_streams, int num_rows,
         return CC_ERR_NO_DEVICE;
     cc_engine* e = new cc_engine();
     e->device = device;
-    (void) hipSetDevice(device);
-    // experiment switch CC_OPT_CU_SPLIT="ins,seg,scan,assoc": the four chains of the pipelined path on disjoint sets of compute units (CU-masked
-    // streams; the mask's bits are dealt round-robin over XCDs and shader engines by the driver, so a contiguous range is spread over the chip)
-    bool cu_split = false;
-    if (const char* cs = std::getenv("CC_ENABLE_ENV_OPTS") ? std::getenv("CC_OPT_CU_SPLIT") : nullptr)
+    StreamSet set;
+    if (hipSetDevice(device) != hipSuccess || !acquire_stream_set(device, &set))
     {
-        int part[4] = {0, 0, 0, 0};
-        hipDeviceProp_t prop;
-        if (sscanf(cs, "%d,%d,%d,%d", &part[0], &part[1], &part[2], &part[3]) == 4 && hipGetDeviceProperties(&prop, device) == hipSuccess)
-        {
-            const int ncu = prop.multiProcessorCount;
-            const int words = (ncu + 31) / 32;
-            auto masked = [&](hipStream_t* out_stream, int from, int cnt) -> bool
-            {
-                std::vector<uint32_t> m(words, 0u);
-                for (int i = from; i < from + cnt && i < ncu; i++)
-                    m[i >> 5] |= 1u << (i & 31);
-                return hipExtStreamCreateWithCUMask(out_stream, (uint32_t) words, m.data()) == hipSuccess;
-            };
-            const int o1 = part[0], o2 = o1 + part[1], o3 = o2 + part[2];
-            cu_split = part[0] > 0 && part[1] > 0 && part[2] > 0 && part[3] > 0 && o3 + part[3] <= ncu && masked(&e->stream, 0, part[0]) &&
-                       masked(&e->stream5, 0, part[0]) && masked(&e->stream7, 0, part[0]) && masked(&e->stream2, o1, part[1]) &&
-                       masked(&e->stream4, o2, part[2]) && masked(&e->stream3, o3, part[3]) && masked(&e->stream6, o3, part[3]);
-            if (!cu_split)
-            {
-                fprintf(stderr, "cc_engine_create: CC_OPT_CU_SPLIT=%s rejected (%d compute units)\n", cs, ncu);
-                give_back_streams(e); // (whatever masked streams were created)
-                delete e;
-                return CC_ERR_INVALID_ARGUMENT;
-            }
-        }
+        delete e;
+        return CC_ERR_HIP;
     }
-    if (cu_split)
-        fprintf(stderr, "cc_engine_create: chains on disjoint compute units (CC_OPT_CU_SPLIT=%s)\n", std::getenv("CC_OPT_CU_SPLIT"));
-    else
-    {
-        StreamSet set;
-        if (hipSetDevice(device) != hipSuccess || !acquire_stream_set(device, &set))
-        {
-            delete e;
-            return CC_ERR_HIP;
-        }
-        e->stream = set.s[0], e->stream2 = set.s[1], e->stream3 = set.s[2], e->stream4 = set.s[3], e->stream5 = set.s[4], e->stream6 = set.s[5], e->stream7 = set.s[6];
-        e->streams_pooled = true;
-    }
+    e->stream = set.s[0], e->stream2 = set.s[1], e->stream3 = set.s[2], e->stream4 = set.s[3], e->stream5 = set.s[4], e->stream6 = set.s[5];
     for (int i = 0; i < 4; i++)
     {
         (void) hipEventCreateWithFlags(&e->ev_ins[i], hipEventDisableTiming);
@@ -2343,7 +2240,6 @@ int cc_engine_create(cc_engine** out, int device, int num_streams, int num_rows,
         (void) hipEventCreateWithFlags(&e->ev_prep[i], hipEventDisableTiming);
         (void) hipEventCreateWithFlags(&e->ev_pubrdy[i], hipEventDisableTiming);
         (void) hipEventCreateWithFlags(&e->ev_rel[i], hipEventDisableTiming);
-        (void) hipEventCreateWithFlags(&e->ev_ego[i], hipEventDisableTiming);
         (void) hipEventCreateWithFlags(&e->ev_rel[i + 4], hipEventDisableTiming);
         if (i == 0)
             (void) hipEventCreateWithFlags(&e->ev_input, hipEventDisableTiming);
@@ -2370,11 +2266,6 @@ int cc_engine_create(cc_engine** out, int device, int num_streams, int num_rows,
     (void) hipFuncSetAttribute((const void*) cck::k_insert2<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void) hipFuncSetAttribute((const void*) (cck::k_insert_par<1, cck::IP_WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
     (void) hipFuncSetAttribute((const void*) (cck::k_insert_par<1, 2 * cck::IP_WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-            e->num_cus = prop.multiProcessorCount;
-    }
     rc = allocate(e);
     if (rc == CC_OK && hipHostMalloc((void**) &e->h_par_left, 8 * sizeof(int)) != hipSuccess)
         rc = CC_ERR_HIP;
@@ -2409,7 +2300,7 @@ int cc_engine_create(cc_engine** out, int device, int num_streams, int num_rows,
     }
     // experiment switches for harnesses that only see the reference's class API (tests/cpp/dropin_demo): CC_OPT_<OPTION>=<value> in the environment
     // (only where CC_ENABLE_ENV_OPTS is set: a library does not change its behaviour on stray environment variables)
-    for (const char* name : {"small_front", "seg_small_max", "fuse_front", "small_graphs"})
+    for (const char* name : {"small_front", "seg_small_max", "fuse_front"})
     {
         if (!getenv("CC_ENABLE_ENV_OPTS"))
             break;
@@ -2437,7 +2328,6 @@ void cc_engine_destroy(cc_engine* e)
     (void) hipStreamSynchronize(e->stream3);
     (void) hipStreamSynchronize(e->stream4);
     (void) hipStreamSynchronize(e->stream6);
-    (void) hipStreamSynchronize(e->stream7);
     (void) hipStreamSynchronize(e->stream5);
     e->deferred_tail = nullptr; // (chains a pipelined call left to "the next call": there is none)
     e->lazy_pending = false;
@@ -2455,7 +2345,6 @@ void cc_engine_destroy(cc_engine* e)
         (void) hipEventDestroy(e->ev_prep[i]);
         (void) hipEventDestroy(e->ev_pubrdy[i]);
         (void) hipEventDestroy(e->ev_rel[i]);
-        (void) hipEventDestroy(e->ev_ego[i]);
         (void) hipEventDestroy(e->ev_rel[i + 4]);
         if (i == 0)
             (void) hipEventDestroy(e->ev_input);
@@ -2536,7 +2425,6 @@ int cc_engine_reset(cc_engine* e, int num_rows)
     CC_HIP_CHECK(e, hipStreamSynchronize(e->stream4));
     CC_HIP_CHECK(e, hipStreamSynchronize(e->stream5));
     CC_HIP_CHECK(e, hipStreamSynchronize(e->stream6));
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream7));
     e->batch_open = false;
     e->idle = true;
     rc = note_released(e, e->call_seq); // (nothing of the old epoch reads the callers' buffers any more)
@@ -3079,8 +2967,6 @@ int cc_engine_set_option(cc_engine* e, const char* name, int64_t value)
         e->mirror_views = value != 0;
     else if (n == "resident_idle_ms")
         e->res_idle_ms = (int) std::max<int64_t>(1, std::min<int64_t>(value, 10000));
-    else if (n == "debug_flags")
-        e->g.debug_flags = (int32_t) value;
     else if (n == "lds_tree_limit")
         e->g.lds_tree_limit = (int32_t) (value < 1 ? 1 : (value > TREE_SLOTS ? TREE_SLOTS : value));
     else if (n == "pipeline")
@@ -3092,8 +2978,6 @@ int cc_engine_set_option(cc_engine* e, const char* name, int64_t value)
         e->allow_graphs = value != 0;
     else if (n == "sub_batch")
         e->sub_batch = value < 0 ? 0 : value;
-    else if (n == "table_on_insert_chain")
-        e->table_on_insert_chain = value < 0 ? 0 : (value > 2 ? 2 : value);
     else if (n == "assoc_sweep_blocks")
         e->assoc_sweep_blocks = value < 1 ? 1 : (value > 1024 ? 1024 : (int) value);
     else if (n == "forget_inclination_table")
@@ -3162,12 +3046,6 @@ int cc_engine_set_option(cc_engine* e, const char* name, int64_t value)
         e->defer_tail_max_streams = value < 0 ? 0 : (int) value;
     else if (n == "assoc_cooldown")
         e->bail_cooldown_batches = value < 0 ? 0 : (value > 1000 ? 1000 : (int) value);
-    else if (n == "ego_on_insert_chain")
-        e->ego_on_insert_chain = value != 0;
-    else if (n == "debug_no_assoc_fallback")
-        e->debug_no_assoc_fallback = value != 0;
-    else if (n == "publish_off_chain")
-        e->publish_off_chain = value != 0;
     else if (n == "timing_every")
         e->timing_every = value < 1 ? 1 : (int) value;
     else if (n == "parallel_insert")
@@ -3185,8 +3063,6 @@ int cc_engine_set_option(cc_engine* e, const char* name, int64_t value)
     }
     else if (n == "insert_split_blocks")
         e->insert_split_blocks = (int) (value < 0 ? 0 : (value > 8 ? 8 : value));
-    else if (n == "insert_narrow_blocks")
-        e->insert_narrow_blocks = value < 0 ? 0 : (value > 8 ? 8 : (int) value);
     else if (n == "insert_wide_max_streams")
         e->insert_wide_max_streams = value < 0 ? 0 : (value > (1 << 20) ? (1 << 20) : (int) value);
     else if (n == "skip_idle_fallbacks")
@@ -3205,8 +3081,6 @@ int cc_engine_set_option(cc_engine* e, const char* name, int64_t value)
     }
     else if (n == "small_direct")
         e->small_direct = value != 0;
-    else if (n == "insert_lds_pad")
-        e->insert_lds_pad_kb = (int) std::max<int64_t>(0, std::min<int64_t>(value, 120));
     else if (n == "check_input_lifetime")
     {
         int rcf = finish_batch(e);
@@ -3242,8 +3116,6 @@ int cc_engine_set_option(cc_engine* e, const char* name, int64_t value)
         e->assoc_batch = value != 0;
     else if (n == "assoc_rounds")
         e->assoc_rounds = (int) (value < 0 ? 0 : (value > 8 ? 8 : value));
-    else if (n == "ego_off_chain")
-        e->ego_off_chain = value != 0;
     else if (n == "scan_store_fin")
         e->scan_store_fin = value < 0 ? -1 : (value ? 1 : 0);
     else if (n == "scan_split")

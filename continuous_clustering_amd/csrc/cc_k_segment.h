@@ -470,7 +470,6 @@ __global__ __launch_bounds__(64, CC_SEGSCAN_MIN_WAVES_PER_SIMD) void k_seg_scan(
     unsigned char* l_out = (unsigned char*) (l_x2 + (tiled ? 4 * 64 * SEG_CH : 64 * PF));
 
     const int lc0 = (int) (tile0 % RC);
-    if (!(g.debug_flags & 1))
     {
         const bool active = lane < ncols;
         const long long gc = tile0 + lane;
@@ -879,7 +878,6 @@ __global__ __launch_bounds__(64, CC_SEGSCAN_MIN_WAVES_PER_SIMD) void k_seg_scan(
         }
     }
     __syncthreads();
-    if (!(g.debug_flags & 4))
     {
         int lc = lc0;
         for (int c = 0; c < ncols; c++)

@@ -297,11 +297,6 @@ int cc_engine_gather_cluster_points(cc_engine* e, int stream, int64_t n, const u
  *                                  (insertion | table, segmentation, window scan | association); 2: the window scan on a fourth chain
  *  "sub_batch"               (0)   firings per pipelined sub-batch of one call; 0: the whole call is one batch
  *  "limit_columns"                 columns one launch may emit per stream before it hands back to the host (continuation passes)
- *  "publish_off_chain"       (1)   pipelined mode: k_publish on a stream of its own instead of at the end of the association chain
- *  "table_on_insert_chain"   (1)   pipelined mode: k_table at the end of the insertion chain; 0: at the head of the segmentation chain; 2: own stream
- *  "ego_on_insert_chain"     (0)   1: k_ego next to k_table instead of in front of k_seg_pre
- *  "ego_off_chain"           (0)   experiment: pipelined mode with the fused front half: k_ego of a batch on the preparation stream, beside the previous
- *                                  batch's insertion, instead of in front of its own insertion (32 streams - 8 .. - 12 %: the event costs more than the kernel)
  *  "input_on_engine_stream"  (0)   1: the caller's device buffers are produced by work enqueued on cc_engine_hip_stream(e) (cc_kitti_convert_frames)
  *  "defer_tail_max_streams"  (96)  launches of at most that many streams leave the chains behind a batch's insertion gate to the NEXT call, which
  *                                  launches them behind its own insertion; every call that reads, synchronises or resets flushes them first; 0: never
@@ -320,8 +315,6 @@ int cc_engine_gather_cluster_points(cc_engine* e, int stream, int64_t n, const u
  *  "insert_wide_max_streams" (160) launches of at most that many streams run k_insert_par with 16 wavefronts per block ...
  *  "insert_split_blocks"     (0)   ... and deal a stream's firings to that many blocks; 0: 8 up to 24 streams, 6 up to 32, 4 up to 40, 3 up to 64,
  *                                  2 up to 96, else 1
- *  "insert_narrow_blocks"    (0)   experiment: that many 4-wavefront blocks per stream above insert_wide_max_streams
- *  "insert_lds_pad"          (0)   experiment: KB of unused dynamic LDS that keep a second insertion block off a compute unit
  *  -- segmentation, window scan ------------------------------------------------------------------------------------------------------------------
  *  "seg_small_max"           (63)  calls of at most that many firings on a sensor of <= 64 rows segment with k_seg_small (rows as lanes)
  *  "scan_packed"                   1: the packed window scan k_scan2 (default above 192 streams per launch and at 128 rows); 0: k_scan
@@ -367,8 +360,6 @@ int cc_engine_gather_cluster_points(cc_engine* e, int stream, int64_t n, const u
  *  "forget_inclination_table"      one-shot action: clear the ground-segmentation inclination table too (the only state cc_engine_reset keeps, like
  *                                  the reference's reset(), cc.cpp:46); used by the drop-in class after its warm-up
  *  -- debugging --------------------------------------------------------------------------------------------------------------------------------------
- *  "debug_flags"             (0)   experiment switches
- *  "debug_no_assoc_fallback" (0)   1: do not launch the serial kernels behind k_assocb (tools only: shows what k_assocb alone covers)
  *  "timing_every"            (1)   with cc_engine_enable_timing on: the ten HIP events bracket every n-th batch only; cc_engine_kernel_times returns
  *                                  the sampled sums scaled to all batches (average launch duration x launches). The events cost 15 - 25 us of the
  *                                  association chain per batch: 3.5 - 5 % of a step at 32 - 64 streams, 1 % at 256 (profiles/r06_ab_timing.txt)

@@ -280,6 +280,25 @@ def test_kernel_variants_give_the_same_result(name, option, value, oracle_lib):
     util.run_and_compare(stream, cfg, chunks=[stream.sensor.num_columns, 211], robot_tf=tf, engine_setup=lambda e: e.set_option(option, value))
 
 
+RETIRED_OPTIONS = ("ego_off_chain", "ego_on_insert_chain", "table_on_insert_chain", "publish_off_chain", "insert_lds_pad", "insert_narrow_blocks",
+                   "debug_no_assoc_fallback", "debug_flags")
+
+
+def test_retired_options_are_rejected(oracle_lib):
+    """Options removed after they measured slower, neutral or wrong by design are unknown names: each is refused, and the engine that refused
+    them still reproduces the oracle."""
+    from continuous_clustering_amd import EngineError
+
+    def setup(e):
+        for name in RETIRED_OPTIONS:
+            with pytest.raises(EngineError, match=f"unknown option {name}$") as err:
+                e.set_option(name, 1)
+            assert err.value.code == capi.CC_ERR_INVALID_ARGUMENT
+
+    stream, cfg, tf = cases.build_case("s64_translate")
+    util.run_and_compare(stream, cfg, chunks=[300], robot_tf=tf, engine_setup=setup)
+
+
 def test_multi_column_insertion_takes_the_steady_part(oracle_lib):
     """VLS-128-shaped stream (every firing spans ~60 columns): after the ring has started, k_insert_multi takes whole calls (debug
     counter 6 = firings taken by the block-parallel kernels)."""
