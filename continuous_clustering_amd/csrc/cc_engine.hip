@@ -482,9 +482,14 @@ int ensure_prep(cc_engine* e, size_t points)
     return CC_OK;
 }
 
+// The events of a timed pass, ev0 .. ev9 in the order they are recorded (launch_batch and its stages name them; resolve_timing turns pairs of
+// them into the seven slots of cc_engine_kernel_times):
+// START | prep | PREP | insert | INSERT ... CHAIN2 | table+segment | SEGMENT | scan | SCAN ... CHAIN3 | assoc_lds | ASSOC_LDS | assoc_global | ASSOC_GLOBAL | publish | PUBLISH
+enum TimingMark { EV_START, EV_PREP, EV_INSERT, EV_CHAIN2, EV_SEGMENT, EV_SCAN, EV_CHAIN3, EV_ASSOC_LDS, EV_ASSOC_GLOBAL, EV_PUBLISH, NEV };
+
 int take_timing_events(cc_engine* e, hipEvent_t* ev)
 {
-    for (int i = 0; i < 10; i++)
+    for (int i = 0; i < NEV; i++)
     {
         if (e->ev_used == e->ev_pool.size())
         {
@@ -642,679 +647,7 @@ __global__ void k_gate_out(const int* __restrict__ left, const int* __restrict__
 
 int finish_batch(cc_engine* e);
 
-// One pass over a batch: insertion on `si`, table + segmentation + window scan on `sb`, association + publish on `sa`
-// (all three equal when not pipelined).
-int launch_batch(cc_engine* e, int first_stream, int count, int64_t n, const float* d_xyz, const uint8_t* d_int,
-                 const double* d_pose, bool first_pass, int slot, hipStream_t si, hipStream_t sb, hipStream_t sa,
-                 hipStream_t sc = nullptr, hipStream_t sp = nullptr, bool prep_done = false)
-{
-    e->idle = false;
-    {
-        const size_t need = (size_t) count * (size_t) n;
-        if (e->ego_capacity < need)
-        {
-            // (old blocks stay in `allocations`; captured small-call graphs hold the old pointers and are dropped)
-            const size_t cap = need < 4096 ? 4096 : need;
-            for (int i = 0; i < 4; i++)
-            {
-                int rce = alloc_plane(e, &e->d_ego[i], cap * cck::EGO_STRIDE);
-                if (rce)
-                    return rce;
-            }
-            e->ego_capacity = cap;
-            e->small_graphs_stale = true;
-        }
-    }
-    if (!sc)
-        sc = sb; // window scan on the segmentation chain unless the four-stage pipeline gives it its own stream
-    if (!sp)
-        sp = si; // preparation on the insertion chain unless it runs ahead on its own stream
-    const Geometry& g = e->g;
-    const auto hp_t0 = std::chrono::steady_clock::now();
-    auto hp_t1 = hp_t0;
-    bool hp_gated = false;
-    const int rpl = (g.num_rows + WAVE - 1) / WAVE;
-    // an upper bound of the columns one pass can emit: the in-kernel limit plus half a rotation of one firing
-    const long long max_cols = std::min<long long>((long long) g.limit_columns + g.num_columns, (long long) g.ring_cols);
-    // grids are (streams, blocks): the stream index is the fast dimension so that one stream's blocks share an XCD (and its L2)
-    dim3 seg_grid((unsigned) count, (unsigned) ((max_cols + 63) / 64));
-    constexpr int NEV = 10;
-    hipEvent_t ev[NEV] = {};
-    const bool mark = e->timing && (e->timing_every <= 1 || e->timing_pass % (uint64_t) e->timing_every == 0);
-    if (e->timing)
-        e->timing_pass++;
-    if (mark)
-    {
-        int rct = take_timing_events(e, ev);
-        if (rct)
-            return rct;
-    }
-    int k = 0;
-#define CC_MARK(st_) \
-    if (mark)        \
-        CC_HIP_CHECK(e, hipEventRecord(ev[k++], st_));
-    // ---- insertion chain -----------------------------------------------------------------------------------------
-    // The head of the batch that has the single-column firing shape is inserted by all wavefronts of a block at once, straight from
-    // the caller's buffers; preparation and the serial kernel then only see what is left (StreamState::cursor).
-    const bool par = first_pass && !prep_done && e->parallel_insert && n >= 64; // (small calls are latency-bound: one kernel less)
-    if (par)
-        sp = si;
-    CC_MARK(sp); // ev0
-    // skip_idle_fallbacks: in steady state k_insert_par takes whole batches and the three kernels behind it (k_insert_multi, k_prep, k_insert2)
-    // have nothing to do — but their blocks wait for free CUs next to the throughput kernels of the other chains, 0.2 - 0.4 ms of chain time per
-    // batch. The host has to wait for the insertion chain before the next batch anyway, so it waits here, for k_insert_par alone, and launches the
-    // others only if some stream's batch was not taken completely (the kernel then leaves the batch descriptor to k_insert2 as before).
-    // (with the fused segmentation also outside the pipelined mode: the fused path needs the counters the gate reads)
-    const bool gate = par && rpl == 1 && (si != sb || e->fuse_front) && e->skip_idle_fallbacks && n <= cck::IP_MAXF && !e->capturing;
-    // Few streams: a step is as long as its insertion chain PLUS the host's launches of the other chains, because the host waits at the gate
-    // before it launches them and the next batch's insertion only starts behind all of that. So the chains behind the gate (`tail` below) of a
-    // batch that needs nothing more on the insertion stream are held back and launched by the NEXT call, after that call has enqueued its own
-    // insertion and before it waits at its gate: the insertion kernels run back to back and the launches hide behind them. Anything that waits
-    // for or reads results launches the held-back chains first (flush_deferred in sync_all).
-    // (launches of many streams only defer together with the lazy gate: that pair is what was measured there)
-    const bool may_defer = gate && first_pass && si != sb && si != sa && e->defer_tail_max_streams > 0 &&
-                           (count <= e->defer_tail_max_streams || (lazy_many_streams(e, count) && lazy_eligible(e, count, n, true, prep_done)));
-    if (!gate)
-    {
-        int rcf = flush_deferred(e);
-        if (rcf)
-            return rcf;
-    }
-    bool fallbacks = true;
-    bool need_segpre = true; // some stream's batch is not closed as fused: k_table / k_seg_pre have work
-    bool ego_done = false;
-    // k_table -> k_seg_scan scratch of this batch-descriptor slot (up to BATCH_SLOTS batches are in flight)
-    Planes Pt = e->P;
-    Pt.tabc += (size_t) slot * (size_t) g.num_streams * (size_t) g.tab_tiles * (size_t) g.num_rows;
-    // per-firing ego transforms of this batch (one buffer per descriptor slot: up to three batches are in flight)
-    double* d_ego = e->d_ego[slot];
-    const bool lazy = may_defer && lazy_eligible(e, count, n, true, prep_done);
-    bool lazy_registered = false;
-    int* const gate_left = e->d_par_left + 2 * slot; // (one pair of counters per batch descriptor slot: the lazy gate reads a batch's pair while the next batch runs)
-    int* const gate_h_left = e->h_par_left + 2 * slot;
-    if (par && rpl == 1) // (two rows per lane = sensors with per-laser azimuth offsets in practice: straight to k_insert_multi)
-    {
-        const bool fuse = gate && e->fuse_front;
-        const double* ego_in = fuse ? (const double*) d_ego : (const double*) nullptr;
-        int* left = gate ? gate_left : (int*) nullptr;
-        const long long cur_ntotal = e->cur_ntotal, cur_f0 = e->cur_f0;
-        // prev_left: the counters of the previous batch's insertion when this one is enqueued before the host has read them (lazy gate)
-        const bool gate_zeroed = gate && first_pass && si != sb && !use_small_front(e, count, n, true); // (submit's k_begin_batch zeroed the counters)
-        auto enqueue_insertion = [=](const int* prev_left, const bool with_remaining) -> int
-        {
-            if (fuse)
-            {
-                // the fused insertion needs the per-firing ego records (they only depend on the caller's poses and the robot transform, which the
-                // host writes between batches): k_ego runs in front of it on the insertion chain. (On the preparation stream, beside the previous
-                // batch's insertion, it measured slower: the cross-stream event costs more than the kernel's ~10 us on the chain.) The records'
-                // buffer belongs to the batch-descriptor slot: its last readers (segmentation chain of four batches ago) are in front of that
-                // slot's publishing event.
-                hipLaunchKernelGGL(cck::k_ego, dim3((unsigned) ((n + 255) / 256), (unsigned) count), dim3(256), 0, si, (const StreamState*) e->d_states, first_stream,
-                                   e->cfg, d_pose, (long long) n, cur_ntotal, cur_f0, d_ego);
-            }
-            if (gate && !gate_zeroed)
-                CC_HIP_CHECK(e, hipMemsetAsync(left, 0, 2 * sizeof(int), si));
-            // few streams: the GPU is not full and the insertion chain is what a step waits for -> twice the wavefronts per block, and the firings of a
-            // stream dealt to several blocks (k_insert_par_fin then finishes the stream's state)
-            if (count <= e->insert_wide_max_streams)
-            {
-                // (round 4: with the segmentation fused in, a block of 8 wavefronts needs ~1.1 ms per 2200 firings by itself: up to 160 streams the
-                // GPU has room for twice the wavefronts — 128 streams 11.3 -> 15.0 G points/s — above that it is full and they only get in each other's way)
-                // (blocks per stream, same-box alternations over 40 steps: 4 up to 40 streams; 3 up to 64 — 48 streams 12.3 -> 12.9 - 13.0 G points/s and 64 streams
-                // 14.0 - 14.2 -> 14.4 - 14.6 against 2 blocks, 4 blocks at 64 streams - 5 %; 2 up to 96 — at 80 streams 3 blocks are 5 - 8 % slower than 2)
-                // A block of 16 wavefronts wants a compute unit it does not share with a block of k_assocb (one per stream, 16 wavefronts too): blocks x streams + streams <= 256
-                // is where more blocks stop paying — 32 streams: 4 / 6 / 7 / 8 blocks 11.3 / 11.7 - 12.0 / 11.6 - 12.0 / 9.7 G points/s; 24 and 16 streams: 8 blocks + 1 .. + 3 % against 4;
-                // 40 streams: 5 blocks - 3 .. - 5 % against 4 (the rule is not exact: measured points decide)
-                const int nb = e->insert_split_blocks > 0 ? e->insert_split_blocks
-                                                          : (count <= 24 ? 8 : (count <= 32 ? 6 : (count <= 40 ? 4 : (count <= 64 ? 3 : (count <= 96 ? 2 : 1)))));
-                hipLaunchKernelGGL((cck::k_insert_par<1, 2 * cck::IP_WAVES>), dim3(count, nb), dim3(128 * cck::IP_WAVES), 0, si, g, e->cfg, Pt, e->d_states,
-                                   first_stream, d_xyz, d_int, d_pose, (long long) n, cur_ntotal, cur_f0, slot, left, ego_in, prev_left);
-                if (nb > 1)
-                    hipLaunchKernelGGL(cck::k_insert_par_fin<1>, dim3(count), dim3(256), 0, si, g, Pt, e->d_states, first_stream, d_xyz, (long long) n,
-                                       cur_ntotal, cur_f0, slot, left, fuse ? 1 : 0, prev_left);
-            }
-            else
-                hipLaunchKernelGGL((cck::k_insert_par<1, cck::IP_WAVES>), dim3(count), dim3(64 * cck::IP_WAVES), 0, si, g, e->cfg, Pt, e->d_states,
-                                   first_stream, d_xyz, d_int, d_pose, (long long) n, cur_ntotal, cur_f0, slot, left, ego_in, prev_left);
-            if (gate)
-            {
-                // (the counter of k_assocb's stops rides along: as of whatever the association chain has finished by now — it only steers a heuristic;
-                // with the lazy gate also the early-stop counter the held-back chains would have copied)
-                hipLaunchKernelGGL(k_gate_out, dim3(1), dim3(64), 0, si, (const int*) left, (const int*) e->d_bail_count, (const int*) e->d_remaining, gate_h_left,
-                                   e->h_bail_count, with_remaining ? e->h_remaining : (int*) nullptr);
-            }
-            return CC_OK;
-        };
-        if (fuse)
-            ego_done = true;
-        if (lazy)
-        {
-            // this batch's insertion goes out before the previous one's counters have been read; what the held-back chains need of the insertion
-            // stream (the early-stop counter, the event the segmentation chain waits for) and the event the NEXT call waits for follow it
-            auto enqueue_lazy = [=](const int* prev_left) -> int
-            {
-                int rci = enqueue_insertion(prev_left, true);
-                if (rci)
-                    return rci;
-                CC_HIP_CHECK(e, hipEventRecord(e->ev_ins[slot], si));
-                CC_HIP_CHECK(e, hipEventRecord(e->ev_gate[slot], si));
-                return CC_OK;
-            };
-            int rcl = enqueue_lazy(e->lazy_pending ? e->lazy_prev_left : nullptr);
-            if (rcl)
-                return rcl;
-            e->lazy_batches += e->lazy_pending ? 1 : 0;
-            CC_MARK(sp); // ev1
-            CC_MARK(si); // ev2
-            // now the previous batch: its counters, the chains behind its insertion — or, if it needs the other insertion kernels, those first and
-            // then this batch's insertion once more (the one above did nothing)
-            const std::function<int()> redo = [=]() -> int
-            {
-                hipLaunchKernelGGL(k_begin_batch, dim3((count + 255) / 256), dim3(256), 0, si, e->d_states, first_stream, count, e->d_remaining, 1, slot,
-                                   (const int*) nullptr, gate_left);
-                return enqueue_lazy(nullptr);
-            };
-            int rcf = flush_deferred(e, &redo);
-            if (rcf)
-                return rcf;
-            e->idle = false; // (the previous batch's closure may have gone through finish_batch / sync_all: this batch's insertion is in flight)
-            fallbacks = false; // (as far as anybody knows: the closure registered below finds out)
-            need_segpre = false;
-            lazy_registered = true;
-        }
-        else
-        {
-            int rci = enqueue_insertion(nullptr, false);
-            if (rci)
-                return rci;
-        }
-        if (gate && !lazy)
-        {
-            {
-                // (this batch's insertion is enqueued: now the chains of the previous batch that were held back)
-                int rcf = flush_deferred(e);
-                if (rcf)
-                    return rcf;
-            }
-            const auto hp1 = std::chrono::steady_clock::now();
-            CC_HIP_CHECK(e, hipStreamSynchronize(si));
-            hp_t1 = std::chrono::steady_clock::now();
-            if (e->host_prof)
-            {
-                e->hp_pre += std::chrono::duration<double>(hp1 - hp_t0).count();
-                e->hp_gate += std::chrono::duration<double>(hp_t1 - hp1).count();
-                hp_gated = true;
-            }
-            fallbacks = gate_h_left[0] != 0;
-            need_segpre = gate_h_left[1] != 0;
-            // an engine that lost the lazy gate (two misses in a row: start-up, sub-rotation batches) gets it back after eight batches in the
-            // steady shape; one more miss then switches it off again at once
-            if (!e->lazy_ok)
-            {
-                e->lazy_clean = (fallbacks || need_segpre) ? 0 : e->lazy_clean + 1;
-                if (e->lazy_clean >= 8)
-                    e->lazy_ok = true, e->lazy_miss = 1, e->lazy_clean = 0;
-            }
-        }
-    }
-    // multi-column firings (per-laser azimuth offsets) and whatever single-column head k_insert_par did not take: block-parallel as well,
-    // with the per-row collision rule checked instead of assumed (option "parallel_insert" = 2 restricts this to the first kernel)
-    // (above 64 rows it is the first insertion kernel, and the gate is here: k_prep and k_insert2<2> — 96 KB of LDS per block — stood 1.3 ms per batch in
-    // the insertion chain of 256 VLS-128-shaped streams, the chain the host waits for, to find nothing to do)
-    const bool gate2 = par && rpl > 1 && e->parallel_insert_multi && si != sb && e->skip_idle_fallbacks;
-    if (par && e->parallel_insert_multi && fallbacks)
-    {
-        if (gate2)
-            CC_HIP_CHECK(e, hipMemsetAsync(e->d_par_left, 0, sizeof(int), si));
-        int* left2 = gate2 ? e->d_par_left : (int*) nullptr;
-        if (rpl == 1)
-            hipLaunchKernelGGL(cck::k_insert_multi<1>, dim3(count), dim3(64 * cck::IM_WAVES), 0, si, g, e->cfg, e->P, e->d_states, first_stream, d_xyz,
-                               d_int, d_pose, (long long) n, (long long) e->cur_ntotal, (long long) e->cur_f0, slot, (int*) nullptr);
-        else
-            hipLaunchKernelGGL(cck::k_insert_multi<2>, dim3(count), dim3(64 * cck::IM_WAVES), 0, si, g, e->cfg, e->P, e->d_states, first_stream, d_xyz,
-                               d_int, d_pose, (long long) n, (long long) e->cur_ntotal, (long long) e->cur_f0, slot, left2);
-        if (gate2)
-        {
-            CC_HIP_CHECK(e, hipMemcpyAsync(e->h_par_left, e->d_par_left, sizeof(int), hipMemcpyDeviceToHost, si));
-            if (e->h_bail_count)
-                CC_HIP_CHECK(e, hipMemcpyAsync(e->h_bail_count, e->d_bail_count, 3 * sizeof(int), hipMemcpyDeviceToHost, si));
-            const auto hp1 = std::chrono::steady_clock::now();
-            CC_HIP_CHECK(e, hipStreamSynchronize(si));
-            hp_t1 = std::chrono::steady_clock::now();
-            if (e->host_prof)
-            {
-                e->hp_pre += std::chrono::duration<double>(hp1 - hp_t0).count();
-                e->hp_gate += std::chrono::duration<double>(hp_t1 - hp1).count();
-                hp_gated = true;
-            }
-            fallbacks = *e->h_par_left != 0;
-        }
-    }
-    // what the held-back chains would still put on the insertion stream is put there now (time marks, the early-stop counter, the event the
-    // segmentation chain waits for): the held-back part must not touch that stream, the next batch's insertion will be on it by then
-    bool pre_done = lazy_registered;
-    const bool defer = may_defer && !fallbacks && !need_segpre && !e->capture_mirror.state;
-    if (defer && !lazy_registered)
-    {
-        CC_MARK(sp); // ev1
-        CC_MARK(si); // ev2
-        CC_HIP_CHECK(e, hipMemcpyAsync(e->h_remaining, e->d_remaining, sizeof(int), hipMemcpyDeviceToHost, si));
-        CC_HIP_CHECK(e, hipEventRecord(e->ev_ins[slot], si));
-        pre_done = true;
-    }
-    // the call this batch is the end of (0: a continuation pass, a sub-batch that is not its call's last, a call on the host path)
-    const uint64_t rel_seq = (first_pass && e->in_submit && e->cur_call_last) ? e->call_seq : 0ull;
-    // (the three arguments: >= 0 replaces what was known when the closure was made — the lazy gate learns them later)
-    auto tail = [=](const int fb_now, const int seg_now, const int pre_now) mutable -> int
-    {
-        if (fb_now >= 0)
-            fallbacks = fb_now != 0;
-        if (seg_now >= 0)
-            need_segpre = seg_now != 0;
-        if (pre_now >= 0)
-            pre_done = pre_now != 0;
-        const bool small_front = first_pass && !prep_done && !par && use_small_front(e, count, n, si != sb);
-        if (small_front)
-        {
-            int rcp = ensure_prep(e, (size_t) n * g.num_rows);
-            if (rcp)
-                return rcp;
-            const Planes Pf = planes_with_prep(e, e->prep_buf);
-            // the whole call in one launch where the results go to pinned memory (the captured graph of cc_engine_add_firings' small calls): the
-            // serial fall-backs, needed once in a long while, are launched by the host when the kernel asks for them (add_firings_small)
-            const bool small_all = e->small_all && e->capture_mirror.state != nullptr && e->capture_mirror.tail_req != nullptr && e->assoc_batch &&
-                                   e->assoc_waves >= 2 && rpl == 1 && e->cfg.cluster_point_trees_every_nth_column == 1;
-            if (small_all)
-            {
-                hipLaunchKernelGGL(cck::k_small_all, dim3(1), dim3(cck::AB_THREADS), cck::insert2_lds_bytes(g.num_rows), si, g, e->cfg, Pf, e->d_states, first_stream,
-                                   slot, d_xyz, d_int, d_pose, (long long) n, e->d_remaining, d_ego, e->d_bail_count, e->capture_mirror);
-                CC_HIP_CHECK(e, hipGetLastError());
-                return CC_OK;
-            }
-            hipLaunchKernelGGL(cck::k_small_front, dim3(1), dim3(256), cck::insert2_lds_bytes(g.num_rows), si, g, e->cfg, Pf, e->d_states, first_stream, slot, d_xyz,
-                               d_int, d_pose, (long long) n, e->d_remaining, d_ego);
-            fallbacks = false;
-            need_segpre = false;
-        }
-        if (first_pass && !prep_done && fallbacks) // relaunch passes of the same batch reuse the staged points; a pipelined caller prepared ahead
-        {
-            int rcp = launch_prep(e, count, n, d_xyz, d_pose, e->prep_buf, sp, e->cur_ntotal, e->cur_f0, par, first_stream);
-            if (rcp)
-                return rcp;
-        }
-        if (!pre_done)
-            CC_MARK(sp); // ev1: prep (with k_insert_par in front of it when that is on)
-        if (sp != si)
-        {
-            CC_HIP_CHECK(e, hipEventRecord(e->ev_prep[slot], sp));
-            CC_HIP_CHECK(e, hipStreamWaitEvent(si, e->ev_prep[slot], 0));
-        }
-        const Planes Pins = planes_with_prep(e, e->prep_buf);
-        if (fallbacks)
-        {
-            const size_t lds = cck::insert2_lds_bytes(g.num_rows);
-            if (rpl == 1)
-                hipLaunchKernelGGL(cck::k_insert2<1>, dim3(count), dim3(128), lds, si, g, e->cfg, Pins, e->d_states, first_stream, slot,
-                                   d_int, (long long) n, e->d_remaining, (long long) e->cur_ntotal, (long long) e->cur_f0);
-            else
-                hipLaunchKernelGGL(cck::k_insert2<2>, dim3(count), dim3(128), lds, si, g, e->cfg, Pins, e->d_states, first_stream, slot,
-                                   d_int, (long long) n, e->d_remaining, (long long) e->cur_ntotal, (long long) e->cur_f0);
-        }
-        if (!pre_done)
-            CC_MARK(si); // ev2: insert
-        if (!pre_done && !e->capture_mirror.state) // (a small call's graph gets the counter through k_publish's mirror)
-            CC_HIP_CHECK(e, hipMemcpyAsync(e->h_remaining, e->d_remaining, sizeof(int), hipMemcpyDeviceToHost, si));
-        // k_table only needs what the insertion of this batch wrote. It is a latency-bound kernel (8 wavefronts per stream) that takes 0.8 ms
-        // when it shares the GPU with the throughput kernels — on the segmentation chain, which is the longest of the three, that is a
-        // third of the chain; at the end of the insertion chain, which has slack, it costs nothing.
-        // calls of a few firings (the per-column latency path): ONE wavefront per stream segments the call's columns, rows as lanes (k_seg_small)
-        const bool seg_small = !par && rpl == 1 && first_pass && n <= e->seg_small_max && !small_front;
-        if (seg_small)
-            need_segpre = false;
-        // (with the fused front half k_insert_par reads and writes the running table `curtab` on the insertion chain: k_table of a batch that is not
-        // fused has to run on that chain too — elsewhere nothing would order it against the next batch's insertion)
-        const bool table_early = si != sb;
-        if (table_early && need_segpre)
-        {
-            if (rpl == 1)
-                hipLaunchKernelGGL(cck::k_table<1>, dim3(count), dim3(64 * cck::TABLE_WAVES), 0, si, g, Pt, e->d_states, first_stream, slot);
-            else
-                hipLaunchKernelGGL(cck::k_table<2>, dim3(count), dim3(64 * cck::TABLE_WAVES), 0, si, g, Pt, e->d_states, first_stream, slot);
-        }
-        if (si != sb)
-        {
-            if (!pre_done)
-                CC_HIP_CHECK(e, hipEventRecord(e->ev_ins[slot], si));
-            CC_HIP_CHECK(e, hipStreamWaitEvent(sb, e->ev_ins[slot], 0));
-        }
-        // ---- table + segmentation + window-scan chain ------------------------------------------------------------
-        CC_MARK(sb); // ev3: start of the second chain
-        if (!table_early && need_segpre)
-        {
-            if (rpl == 1)
-                hipLaunchKernelGGL(cck::k_table<1>, dim3(count), dim3(64 * cck::TABLE_WAVES), 0, sb, g, Pt, e->d_states, first_stream, slot);
-            else
-                hipLaunchKernelGGL(cck::k_table<2>, dim3(count), dim3(64 * cck::TABLE_WAVES), 0, sb, g, Pt, e->d_states, first_stream, slot);
-        }
-        if (!ego_done && need_segpre)
-            hipLaunchKernelGGL(cck::k_ego, dim3((unsigned) ((n + 255) / 256), (unsigned) count), dim3(256), 0, sb, (const StreamState*) e->d_states, first_stream,
-                           e->cfg, d_pose, (long long) n, (long long) e->cur_ntotal, (long long) e->cur_f0, d_ego);
-        if (!need_segpre)
-            ;
-        else if (rpl == 1)
-            hipLaunchKernelGGL(cck::k_seg_pre<1>, dim3((unsigned) count, cck::SEGPRE_BLOCKS), dim3(64), 0, sb, g, e->cfg, Pt, e->d_states,
-                               first_stream, slot, d_pose, (long long) e->cur_ntotal, (long long) e->cur_f0, (const double*) d_ego, (long long) n);
-        else
-            hipLaunchKernelGGL(cck::k_seg_pre<2>, dim3((unsigned) count, cck::SEGPRE_BLOCKS), dim3(64), 0, sb, g, e->cfg, Pt, e->d_states,
-                               first_stream, slot, d_pose, (long long) e->cur_ntotal, (long long) e->cur_f0, (const double*) d_ego, (long long) n);
-        if (seg_small)
-        {
-            hipLaunchKernelGGL(cck::k_ego, dim3((unsigned) ((n + 255) / 256), (unsigned) count), dim3(256), 0, sb, (const StreamState*) e->d_states, first_stream,
-                               e->cfg, d_pose, (long long) n, (long long) e->cur_ntotal, (long long) e->cur_f0, d_ego);
-            hipLaunchKernelGGL(cck::k_seg_small, dim3((unsigned) count), dim3(64), 0, sb, g, e->cfg, e->P, e->d_states, first_stream, slot, d_pose,
-                               (long long) e->cur_ntotal, (long long) e->cur_f0, (const double*) d_ego, (long long) n);
-        }
-        else if (!small_front)
-        {
-            const size_t lds = cck::seg_scan_lds_bytes(g.num_rows);
-            hipLaunchKernelGGL(cck::k_seg_scan, seg_grid, dim3(64), lds, sb, g, e->cfg, Pt, e->d_states, first_stream, slot); // (Pt: this slot's table carries)
-        }
-        if (sc != sb)
-        {
-            CC_HIP_CHECK(e, hipEventRecord(e->ev_segscan[slot], sb));
-            CC_HIP_CHECK(e, hipStreamWaitEvent(sc, e->ev_segscan[slot], 0));
-        }
-        CC_MARK(sc); // ev4: table + segment (start of the window scan)
-        // ---- what the association chain of this batch will be (decided here: the window scan writes Planes::sc_fin only for the serial kernels) ----
-        bool batch_assoc = e->assoc_batch && e->cfg.cluster_point_trees_every_nth_column == 1;
-        // Streams on which k_assocb keeps stopping (vegetation: more trees born per group than it has lanes for) cost a batch more with it than
-        // without: every stop is a (batch-parallel, serial) round, and a launch lasts as long as its slowest stream — the one that went serial.
-        // While at least a quarter of a launch's streams stop per batch the serial kernels run alone; every ninth batch tries again.
-        if (batch_assoc && e->assoc_rounds == 0 && e->h_bail_count && !e->capturing && count >= 8)
-        {
-            const int seen_now = *e->h_bail_count;
-            if (e->chronic_skip > 0)
-            {
-                e->chronic_skip--;
-                e->bail_seen = seen_now;
-                batch_assoc = false;
-                // (the batches that try again must not meet the two sweeping blocks the serial kernel runs as behind an idle k_assocb)
-                if (e->chronic_skip == 0)
-                    e->bail_cooldown = e->bail_cooldown_batches > 2 ? e->bail_cooldown_batches : 2;
-            }
-            else if ((seen_now - e->chronic_seen) * 4 >= count && e->chronic_probe)
-                e->chronic_skip = 8;
-            e->chronic_probe = batch_assoc; // (the counter read behind the NEXT batch tells what this one did)
-            e->chronic_seen = seen_now;
-        }
-        int adaptive_rounds = 1;
-        if (e->assoc_rounds == 0 && e->h_bail_count && !e->capturing)
-        {
-            const int seen = *e->h_bail_count; // (as of some earlier batch: a heuristic, not a condition of correctness)
-            if (seen != e->bail_seen)
-            {
-                e->bail_seen = seen;
-                e->bail_cooldown = e->bail_cooldown_batches;
-            }
-            if (e->bail_cooldown > 0)
-            {
-                e->bail_cooldown--;
-                adaptive_rounds = 3;
-            }
-        }
-        // The serial kernels read a point's finished_at contribution from Planes::sc_fin or recompute it (cc_k_base.h: cell_fin_of). Behind the
-        // batch-parallel kernel they find nothing to do, and the scan saves the 8 bytes per cell; where they are expected to associate (the
-        // batch-parallel kernel off, pinned rounds, stops lately) the scan stores them. A small call's front kernel has scanned with the engine's
-        // geometry (never stored).
-        Geometry gs = g;
-        gs.scan_stores_fin = (!small_front && !(batch_assoc && e->assoc_rounds == 0 && adaptive_rounds == 1)) ? 1 : 0;
-        if (e->scan_store_fin >= 0 && !small_front)
-            gs.scan_stores_fin = e->scan_store_fin;
-        const dim3 scan_grid((unsigned) count, cck::SCAN_BLOCKS);
-        bool use_split = false;
-        if (small_front)
-            ; // (k_small_front has scanned the call's columns)
-        // (65 - 128 rows: packed by default. The lock-step form with two rows per lane — scan_packed = 0 — shortens the scan's own launch, 3.0 -> 2.35 ms at
-        // 256 x S128, but needs more vector instructions, and the step is bound by those: 11.7 -> 11.4 G points/s same-box)
-        // (64 rows, end of round 4: with the insertion's uniform work on the scalar unit the step follows the vector-instruction count, and the packed
-        // scan issues 0.65 x those of the lock-step one: + 3 % at 256 streams (same-box, 3 alternations: 16.22 -> 16.72 G points/s), - 1 ... - 2 % at
-        // 32 - 128 streams where the GPU has room and the lock-step scan's shorter launch counts)
-        else if ([&]() -> bool
-                 {
-                     // the long scans apart? scan_split 1: always (with the packed scan); 2 (default): while they are a large part of the scan's work. The
-                     // visits k_scan2_long makes per column (of 64 rows) say so: vegetation ~150, the 128-row bench scene ~15, the street scene ~4. Where they
-                     // are few the split costs chain time (two more launches whose blocks wait for wave slots, the longest single scan standing alone: street
-                     // scene - 8 % at 256 streams, the 128-row scene - 2 %), on vegetation it is + 60 .. + 70 %. Every 32nd batch is scanned packed and with
-                     // the split, which counts; the batches counted since the last look decide (on above 40 visits per column, off again below 20).
-                     // On vegetation the packed scan with the split also beats the lock-step scan from 48 streams per launch (64 streams + 14 %, 128 + 38 %;
-                     // 32 streams - 4 %), where the street scene wants the lock-step one up to 192.
-                     const bool packed_default = e->scan_packed == 1 || (e->scan_packed < 0 && (rpl > 1 || count > 192));
-                     use_split = false;
-                     if (g.mirror_fields || e->scan_split == 0)
-                         return packed_default;
-                     if (e->scan_split == 1 || !e->h_bail_count || e->capturing)
-                     {
-                         use_split = packed_default && e->scan_split == 1;
-                         return packed_default;
-                     }
-                     const unsigned vis = (unsigned) e->h_bail_count[1], cols = (unsigned) e->h_bail_count[2];
-                     const unsigned dc = cols - e->split_cols_seen, dv = vis - e->split_rec_seen;
-                     if (dc >= 1024u)
-                     {
-                         const double rate = (double) dv / ((double) dc * (double) rpl); // (per column of 64 rows)
-                         e->split_on = e->split_on ? rate > 20.0 : rate > 40.0;
-                         e->split_cols_seen = cols, e->split_rec_seen = vis;
-                     }
-                     const bool probe = (e->split_probe++ & 31u) == 0u;
-                     const bool promote = !packed_default && e->scan_packed < 0 && rpl == 1 && count >= 48; // (launches the lock-step scan would take)
-                     use_split = (e->split_on || probe) && (packed_default || promote);
-                     return packed_default || (promote && use_split);
-                 }())
-        {
-            const bool split = use_split;
-            if (split)
-            {
-                // long scans apart (cc_k_scan.h): the packed scan hands points that are still scanning after SCAN_CAP visits to k_scan2_long, which
-                // keeps every lane busy with one of them; k_scan2_epi finishes the columns that had such a point
-                const dim3 long_grid((unsigned) count, cck::SCAN_LONG_BLOCKS), epi_grid((unsigned) count, cck::SCAN_EPI_BLOCKS);
-                if (rpl == 1)
-                {
-                    hipLaunchKernelGGL((cck::k_scan2<1, false, true>), scan_grid, dim3(64), 0, sc, gs, e->cfg, e->P, e->d_states, first_stream, slot);
-                    hipLaunchKernelGGL(cck::k_scan2_long<1>, long_grid, dim3(64), 0, sc, g, e->cfg, e->P, e->d_states, first_stream, slot, e->d_bail_count);
-                    hipLaunchKernelGGL(cck::k_scan2_epi<1>, epi_grid, dim3(64), 0, sc, g, e->cfg, e->P, e->d_states, first_stream, slot, e->d_bail_count);
-                }
-                else
-                {
-                    hipLaunchKernelGGL((cck::k_scan2<2, false, true>), scan_grid, dim3(64), 0, sc, gs, e->cfg, e->P, e->d_states, first_stream, slot);
-                    hipLaunchKernelGGL(cck::k_scan2_long<2>, long_grid, dim3(64), 0, sc, g, e->cfg, e->P, e->d_states, first_stream, slot, e->d_bail_count);
-                    hipLaunchKernelGGL(cck::k_scan2_epi<2>, epi_grid, dim3(64), 0, sc, g, e->cfg, e->P, e->d_states, first_stream, slot, e->d_bail_count);
-                }
-            }
-            else if (rpl == 1 && !g.mirror_fields)
-                hipLaunchKernelGGL((cck::k_scan2<1, false>), scan_grid, dim3(64), 0, sc, gs, e->cfg, e->P, e->d_states, first_stream, slot);
-            else if (rpl == 1)
-                hipLaunchKernelGGL((cck::k_scan2<1, true>), scan_grid, dim3(64), 0, sc, gs, e->cfg, e->P, e->d_states, first_stream, slot);
-            else if (!g.mirror_fields)
-                hipLaunchKernelGGL((cck::k_scan2<2, false>), scan_grid, dim3(64), 0, sc, gs, e->cfg, e->P, e->d_states, first_stream, slot);
-            else
-                hipLaunchKernelGGL((cck::k_scan2<2, true>), scan_grid, dim3(64), 0, sc, gs, e->cfg, e->P, e->d_states, first_stream, slot);
-        }
-        else if (rpl == 1 && !g.mirror_fields)
-            hipLaunchKernelGGL((cck::k_scan<1, false>), scan_grid, dim3(64), 0, sc, gs, e->cfg, e->P, e->d_states, first_stream, slot);
-        else if (rpl == 1)
-            hipLaunchKernelGGL((cck::k_scan<1, true>), scan_grid, dim3(64), 0, sc, gs, e->cfg, e->P, e->d_states, first_stream, slot);
-        else if (!g.mirror_fields)
-            hipLaunchKernelGGL((cck::k_scan<2, false>), scan_grid, dim3(64), 0, sc, gs, e->cfg, e->P, e->d_states, first_stream, slot);
-        else
-            hipLaunchKernelGGL((cck::k_scan<2, true>), scan_grid, dim3(64), 0, sc, gs, e->cfg, e->P, e->d_states, first_stream, slot);
-        CC_MARK(sc); // ev5: scan
-        if (sc != sa)
-        {
-            CC_HIP_CHECK(e, hipEventRecord(e->ev_seg[slot], sc));
-            CC_HIP_CHECK(e, hipStreamWaitEvent(sa, e->ev_seg[slot], 0));
-        }
-        // ---- association + publish chain -------------------------------------------------------------------------
-        CC_MARK(sa); // ev6: start of the third chain
-        // batch-parallel association in front of the serial kernels: it takes every group of columns in which nothing can differ from the
-        // reference's sequential semantics (cc_assocb.h) and stops in front of the first group that might. With k_assoc3 behind it the pair runs
-        // assoc_rounds times: a LIMITED launch of the serial kernel takes that one group, the batch-parallel kernel continues behind it; the last
-        // serial launch takes whatever is left of the batch.
-        auto launch_assocb = [&]()
-        {
-            if (rpl == 1)
-                hipLaunchKernelGGL(cck::k_assocb<1>, dim3(count), dim3(cck::AB_THREADS), 0, sa, g, e->cfg, e->P, e->d_states, first_stream, slot,
-                                   e->d_bail_count);
-            else
-                hipLaunchKernelGGL(cck::k_assocb<2>, dim3(count), dim3(cck::AB_THREADS), 0, sa, g, e->cfg, e->P, e->d_states, first_stream, slot,
-                                   e->d_bail_count);
-        };
-        bool marked7 = false;
-        bool global_done = false; // k_associate's work was done inside the last k_assoc3 launch
-        // a lean small call (k_small_front in front, results mirrored): k_assocb, then ONE kernel for the serial fall-backs, the ids and the mirror
-        const bool small_tail = small_front && e->capture_mirror.state != nullptr && batch_assoc && e->assoc_waves >= 2 && rpl == 1 &&
-                                e->cfg.cluster_point_trees_every_nth_column == 1;
-        if (small_tail)
-        {
-            launch_assocb();
-            CC_MARK(sa); // ev7
-            marked7 = true;
-            hipLaunchKernelGGL(cck::k_small_tail<1>, dim3(1), dim3(cck::A3_THREADS), 0, sa, g, e->cfg, e->P, e->d_states, first_stream, slot, e->capture_mirror);
-            global_done = true;
-        }
-        // k_assoc3 walks the finished-cluster checks of several columns at once and assumes one check per column
-        else if (e->assoc_waves >= 2 && e->cfg.cluster_point_trees_every_nth_column == 1)
-        {
-            // with or without the links wave (cc_assoc3.h: A3_THREADS): by default (assoc_waves = 0) with it while the streams are few
-            // enough for the association chain to be what the step waits for
-            const bool lwave = e->assoc_waves == 4 || (e->assoc_waves_auto && count <= CC_LWAVE_MAX_STREAMS);
-            const dim3 block(lwave ? cck::A3_THREADS : 192);
-            const int rounds = batch_assoc ? (e->assoc_rounds > 0 ? e->assoc_rounds : adaptive_rounds) : 1;
-            for (int r = 0; r < rounds; r++)
-            {
-                if (batch_assoc)
-                {
-                    launch_assocb();
-                    if (r == 0)
-                    {
-                        CC_MARK(sa); // ev7: the batch-parallel kernel alone ("assoc_lds_ms"); the serial kernels behind it count as "assoc_global_ms"
-                        marked7 = true;
-                    }
-                }
-                const int limited = r + 1 < rounds ? 1 : 0;
-                // behind k_assocb the serial kernel is a safety net that finds nothing to do: a few blocks sweep over all streams instead of one block
-                // per stream waiting for 45 KB of LDS on a busy CU. One block per stream when it is what associates, or while k_assocb has had to stop
-                // lately (adaptive_rounds > 1), or when the caller pinned the number of rounds
-                const int blocks = (batch_assoc && e->assoc_rounds == 0 && adaptive_rounds == 1 && !e->capturing) ? (count < e->assoc_sweep_blocks ? count : e->assoc_sweep_blocks) : count;
-                if (rpl == 1)
-                    hipLaunchKernelGGL(cck::k_assoc3<1>, dim3(blocks), block, 0, sa, gs, e->cfg, e->P, e->d_states, first_stream, slot, limited, count, 1);
-                else
-                    hipLaunchKernelGGL(cck::k_assoc3<2>, dim3(blocks), block, 0, sa, gs, e->cfg, e->P, e->d_states, first_stream, slot, limited, count, 1);
-                global_done = limited == 0; // (the last launch of k_assoc3 takes the streams that continue in global memory with it)
-            }
-        }
-        else
-        {
-            if (batch_assoc)
-            {
-                launch_assocb();
-                CC_MARK(sa);
-                marked7 = true;
-            }
-            if (rpl == 1)
-                hipLaunchKernelGGL(cck::k_assoc_lds<1>, dim3(count), dim3(64), 0, sa, gs, e->cfg, e->P, e->d_states, first_stream, slot);
-            else
-                hipLaunchKernelGGL(cck::k_assoc_lds<2>, dim3(count), dim3(64), 0, sa, gs, e->cfg, e->P, e->d_states, first_stream, slot);
-        }
-        if (!marked7)
-            CC_MARK(sa); // ev7: assoc_lds (without the batch-parallel kernel: the serial LDS kernel)
-        // streams whose unfinished trees do not fit the LDS pool (or exotic window configs) continue in global memory
-        if (global_done)
-            ;
-        else if (rpl == 1)
-            hipLaunchKernelGGL(cck::k_associate<1>, dim3(count), dim3(64), 0, sa, g, e->cfg, e->P, e->d_states, first_stream, slot);
-        else
-            hipLaunchKernelGGL(cck::k_associate<2>, dim3(count), dim3(64), 0, sa, g, e->cfg, e->P, e->d_states, first_stream, slot);
-        CC_MARK(sa); // ev8: assoc_global
-        // (without the host synchronisation behind k_insert_par nobody else reads the counter of k_assocb's stops: four bytes ride along here)
-        if (batch_assoc && !gate && !gate2 && e->h_bail_count && !e->capturing)
-            CC_HIP_CHECK(e, hipMemcpyAsync(e->h_bail_count, e->d_bail_count, 3 * sizeof(int), hipMemcpyDeviceToHost, sa));
-        // The ids of the published columns only read what the association of THIS batch left behind (tree root of every cell, cluster id
-        // at the root cell; neither is touched again before the ring wraps), so in the pipelined mode they are written on a stream of their
-        // own and the next batch's association starts without waiting for them.
-        hipStream_t spub = si != sa ? e->stream6 : sa;
-        if (spub != sa)
-        {
-            CC_HIP_CHECK(e, hipEventRecord(e->ev_pubrdy[slot], sa));
-            CC_HIP_CHECK(e, hipStreamWaitEvent(spub, e->ev_pubrdy[slot], 0));
-        }
-        if (!small_tail)
-            hipLaunchKernelGGL(cck::k_publish, dim3((unsigned) count, cck::PUBLISH_BLOCKS), dim3(64), 0, spub, g, e->P, e->d_states, first_stream,
-                               slot, e->capture_mirror);
-        CC_MARK(spub); // ev9: publish
-        if (si != sa)
-        {
-            CC_HIP_CHECK(e, hipEventRecord(e->ev_assoc[slot], spub)); // the batch descriptor slot is free again after its publish
-            e->assoc_pending[slot] = true;
-            if (rel_seq)
-            {
-                // every kernel that reads the call's input buffers is ordered in front of this point (insertion -> segmentation -> association -> publish)
-                CC_HIP_CHECK(e, hipEventRecord(e->ev_rel[rel_seq % cc_engine::REL_RING], spub));
-                e->rel_recorded[rel_seq % cc_engine::REL_RING] = rel_seq;
-            }
-        }
-        CC_HIP_CHECK(e, hipGetLastError());
-        if (e->host_prof && hp_gated)
-        {
-            e->hp_post += std::chrono::duration<double>(std::chrono::steady_clock::now() - hp_t1).count();
-            e->hp_calls++;
-        }
-        return CC_OK;
-    };
-#undef CC_MARK
-    if (lazy_registered)
-    {
-        const long long my_ntotal = e->cur_ntotal, my_f0 = e->cur_f0;
-        const int my_prep_buf = e->prep_buf;
-        e->deferred_tail = [=](const std::function<int()>* redo) mutable -> int
-        {
-            CC_HIP_CHECK(e, hipEventSynchronize(e->ev_gate[slot]));
-            const bool fb = gate_h_left[0] != 0, seg = gate_h_left[1] != 0;
-            if (!fb && !seg)
-            {
-                e->lazy_miss = 0;
-                return tail(0, 0, 1);
-            }
-            // some stream's batch was not taken completely (or is not fused): the other insertion kernels / k_table and k_seg_pre, then the chains,
-            // then — a call of limit_columns — the continuation passes; all of it with this batch's buffers, not the next one's
-            if (++e->lazy_miss >= 2)
-                e->lazy_ok = false; // (streams that are not in the steady single-column shape: the plain gate from now on)
-            const long long keep_ntotal = e->cur_ntotal, keep_f0 = e->cur_f0;
-            const int keep_buf = e->prep_buf;
-            e->cur_ntotal = my_ntotal, e->cur_f0 = my_f0, e->prep_buf = my_prep_buf;
-            int rc = tail(fb ? 1 : 0, seg ? 1 : 0, 0);
-            if (!rc && hipStreamSynchronize(si) != hipSuccess)
-                rc = CC_ERR_HIP;
-            if (!rc && *e->h_remaining != 0)
-                rc = finish_batch(e);
-            e->cur_ntotal = keep_ntotal, e->cur_f0 = keep_f0, e->prep_buf = keep_buf;
-            if (!rc && redo)
-            {
-                e->lazy_redone++;
-                rc = (*redo)();
-            }
-            return rc;
-        };
-        e->lazy_pending = true;
-        e->lazy_prev_left = gate_left;
-        return CC_OK;
-    }
-    if (defer)
-    {
-        e->deferred_tail = [tail](const std::function<int()>*) mutable -> int { return tail(-1, -1, -1); };
-        return CC_OK;
-    }
-    return tail(-1, -1, -1);
-}
+#include "cc_launch.h" // the stages of a batch and launch_batch
 
 __global__ void k_clear_remaining(int* remaining)
 {
@@ -1336,10 +669,9 @@ int collect_links(cc_engine* e, int stream, const StreamState& st);
 
 int resolve_timing(cc_engine* e)
 {
-    // 10 events per pass: ev0 | prep | ev1 | insert | ev2 ... ev3 | table+segment | ev4 | scan | ev5 ... ev6 | assoc_lds | ev7 |
-    // assoc_global | ev8 | publish | ev9
-    static const int from[7] = {0, 1, 3, 4, 6, 7, 8};
-    for (size_t i = 0; i + 9 < e->ev_used; i += 10)
+    // NEV events per pass (TimingMark); slot k of kernel_ms is the time from mark from[k] to the mark behind it
+    static const int from[7] = {EV_START, EV_PREP, EV_CHAIN2, EV_SEGMENT, EV_CHAIN3, EV_ASSOC_LDS, EV_ASSOC_GLOBAL};
+    for (size_t i = 0; i + NEV - 1 < e->ev_used; i += NEV)
     {
         for (int k = 0; k < 7; k++)
         {

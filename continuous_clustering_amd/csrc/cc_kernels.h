@@ -1,6 +1,8 @@
 // cc_kernels.h — the hand-written gfx950 kernels of the continuous-clustering hot path, by stage (all in namespace cck, wave64, compiled with
 // -ffp-contract=off: every floating-point expression keeps the reference's operation order, nothing is fused into FMAs the x86 reference does not
-// have). One translation unit (cc_engine.hip) includes this file; the order below is the order of definition.
+// have). One translation unit (cc_engine.hip) includes this file; the order below is the order of definition. The engine launches them from one
+// function per stage of a batch (cc_launch.h: enqueue_fused_insertion ... publish_and_release, called by launch_batch / launch_tail); kernels
+// templated on the rows per lane go through CC_LAUNCH_RPL there.
 //
 //   cc_k_base.h          wave-level helpers: DPP reductions, relaxed LDS accessors, wave-uniform values, per-stream plane pointers
 //   cc_k_segcells.h      seg_pre_cells: the per-cell part of the ground segmentation (cc.cpp:294-624), shared by insertion and segmentation
