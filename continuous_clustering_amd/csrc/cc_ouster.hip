@@ -1,16 +1,21 @@
-// cc_ouster.hip — Ouster LEGACY lidar packets -> engine firings on gfx950 (include/cc_ouster.h).
+// cc_ouster.hip — Ouster lidar packets (LEGACY, RNG19_RFL8_SIG16_NIR16 and its _DUAL UDP profile) -> engine firings on gfx950
+// (include/cc_ouster.h, include/cc_ouster_profiles.h).
 //
 // One kernel, k_ouster_decode, one 256-thread workgroup per (packet, stream). Pure streaming:
-//   1. the packet (C * (20 + 12 H) bytes, 6464 B for an OS-32) is staged into LDS with 16-byte loads (pixels sit at a 12-byte stride,
-//      so per-lane loads straight from HBM would be three dword loads at odd alignment);
+//   1. the packet (header + C columns + footer, 6464 B for a LEGACY OS-32) is staged into LDS with 16-byte loads (pixels sit at a 12-byte
+//      stride, or at 16 bytes from a 4-byte-aligned base, so per-lane loads straight from HBM would be dword loads at odd alignment);
 //   2. wave 0 reads the C column headers from LDS (status, measurement id) and decides which columns become placeholders;
 //   3. every lane then writes 16 contiguous bytes of the packet's output regions: C*H*12 B of xyz (the C firings of a packet are adjacent
 //      in [S][n][H][3]), C*H B of intensity, C*96 B of replicated poses. The LUT rows a column reads ([m_id][row][3], 12 H bytes) are
 //      contiguous too and are read as float4; the whole LUT (W*H*24 B, 786 KB for 32 x 1024) stays in L2.
-// HBM bytes per packet: read C*(20 + 12 H) + 96, write C*(13 H + 96 + 4): 12.4 B read and 14.5 B written per cell for 64 x 16.
+// HBM bytes per packet: written C*(13 H + 96 + 4) for every profile (14.5 B per cell for 64 x 16); read, with the 96 B packet pose,
+//   LEGACY                       C*(20 + 12 H) + 96        12.4 B per cell for 64 x 16
+//   RNG19_RFL8_SIG16_NIR16       C*(12 + 12 H) + 64 + 96   12.3 B per cell
+//   RNG19_RFL8_SIG16_NIR16_DUAL  C*(12 + 16 H) + 64 + 96   16.3 B per cell (the second return is staged with its packet and never read)
 //
-// The layout lives in one descriptor (PacketLayout) so that another UDP profile is one more table row. Device code is built with
-// -ffp-contract=off and spells the cartesianT arithmetic with __fmul_rn / __fadd_rn anyway: x = (float) r * d + o, two roundings.
+// The layout lives in one descriptor per profile (PacketLayout, LAYOUTS) that the kernel takes by value: its fields are kernel arguments,
+// uniform over the grid, so no lane branches on the profile. Device code is built with -ffp-contract=off and spells the cartesianT
+// arithmetic with __fmul_rn / __fadd_rn anyway: x = (float) r * d + o, two roundings.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -21,6 +26,7 @@
 
 #include "../../include/cc_hip.h"
 #include "../../include/cc_ouster.h"
+#include "../../include/cc_ouster_profiles.h"
 
 namespace
 {
@@ -41,29 +47,52 @@ int fail(int code, const std::string& what)
             return fail(CC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(err__));             \
     } while (0)
 
-// Byte layout of one column of a UDP profile (offsets within the column; H = pixels per column).
+// Byte layout of a packet of one UDP profile (column offsets are within the column; H = pixels per column).
 struct PacketLayout
 {
-    int header_bytes;       // column header before the first pixel
-    int pixel_stride;       // bytes per pixel
-    int range_offset;       // u32 range within a pixel
-    uint32_t range_mask;    // range bits (millimetres)
-    int signal_offset;      // u16 signal within a pixel
-    int measurement_offset; // u16 measurement id within the header
-    int status_bytes;       // u32 status after the last pixel
-    uint32_t status_valid;  // column is valid iff status & status_valid (ouster_input.hpp:120-125)
+    int packet_header_bytes; // before the first column; as many bytes follow the last column (neither is ever looked at)
+    int header_bytes;        // column header before the first pixel
+    int pixel_stride;        // bytes per pixel
+    int range_offset;        // u32 range within a pixel
+    uint32_t range_mask;     // range bits (millimetres)
+    int signal_offset;       // u16 signal within a pixel
+    int measurement_offset;  // u16 measurement id within the header
+    int status_offset;       // status within the column; -1: behind the last pixel (header_bytes + pixel_stride * H)
+    int status_bytes;        // 4: u32 status, 2: u16 status
+    int trailer_bytes;       // bytes of the column behind the last pixel
+    uint32_t status_valid;   // column is valid iff status & status_valid (ouster_input.hpp:120-125)
 };
 
-// LEGACY (the profile of the reference's calibrations/touareg_os32_*.json), restated from the SDK's packet_format: UNPINNED.
-constexpr PacketLayout LAYOUT_LEGACY = {16, 12, 0, 0x000FFFFFu, 6, 8, 4, 0x1u};
+// Restated from the SDK's packet_format and field tables: UNPINNED, all three (include/cc_ouster_profiles.h has the table). LEGACY is the
+// profile of the reference's calibrations/touareg_os32_*.json. Indexed by the CC_OUSTER_PROFILE_* enum.
+constexpr PacketLayout LAYOUTS[] = {
+    {0, 16, 12, 0, 0x000FFFFFu, 6, 8, -1, 4, 4, 0x1u},  // LEGACY
+    {32, 12, 12, 0, 0x0007FFFFu, 6, 8, 10, 2, 0, 0x1u}, // RNG19_RFL8_SIG16_NIR16
+    {32, 12, 16, 0, 0x0007FFFFu, 8, 8, 10, 2, 0, 0x1u}, // RNG19_RFL8_SIG16_NIR16_DUAL (first return only, as the reference)
+};
+constexpr int NUM_PROFILES = sizeof(LAYOUTS) / sizeof(LAYOUTS[0]);
 
 constexpr int BLOCK = 256;
 constexpr int MAX_ROWS = 128;
 constexpr int MAX_COLUMNS_PER_PACKET = 64; // wave 0 holds one column header per lane
+constexpr int64_t MAX_LDS_BYTES = 65536;   // of one workgroup: the staged packet and s_mid
 
 int column_bytes(const PacketLayout& L, int H)
 {
-    return L.header_bytes + L.pixel_stride * H + L.status_bytes;
+    return L.header_bytes + L.pixel_stride * H + L.trailer_bytes;
+}
+
+int64_t packet_bytes_of(const PacketLayout& L, int H, int C)
+{
+    return 2 * (int64_t) L.packet_header_bytes + (int64_t) C * column_bytes(L, H);
+}
+
+// The layout with status_offset resolved for H rows (what the kernel takes).
+PacketLayout resolved(PacketLayout L, int H)
+{
+    if (L.status_offset < 0)
+        L.status_offset = L.header_bytes + L.pixel_stride * H;
+    return L;
 }
 
 struct StreamLut
@@ -116,7 +145,7 @@ __global__ __launch_bounds__(BLOCK) void k_ouster_decode(DecodeArgs a)
     const PacketLayout& L = a.L;
     const size_t pk = (size_t) s * a.n_packets + p;
     const bool skipped = a.skip && a.skip[pk];
-    const unsigned char* sb = (const unsigned char*) s_pkt;
+    const unsigned char* sb = (const unsigned char*) s_pkt + L.packet_header_bytes; // column 0
 
     // 1. stage the packet
     if (!skipped)
@@ -140,7 +169,7 @@ __global__ __launch_bounds__(BLOCK) void k_ouster_decode(DecodeArgs a)
         if (tid < C && !skipped)
         {
             const unsigned char* col = sb + tid * a.col_bytes;
-            const uint32_t status = lds_u32(col + L.header_bytes + L.pixel_stride * H);
+            const uint32_t status = L.status_bytes == 4 ? lds_u32(col + L.status_offset) : lds_u16(col + L.status_offset);
             const int mid = (int) lds_u16(col + L.measurement_offset);
             invalid = !(status & L.status_valid);
             bad_mid = !invalid && mid >= lut.columns; // the reference would read its LUT out of bounds
@@ -244,6 +273,8 @@ struct cc_ouster
     int columns_per_packet = 0;
     int max_packets = 0;
     int packet_bytes = 0;
+    int profile = CC_OUSTER_PROFILE_LEGACY;
+    PacketLayout layout = LAYOUTS[CC_OUSTER_PROFILE_LEGACY]; // resolved for `rows`
     hipStream_t stream = nullptr;
     bool own_stream = false;
     StreamLut* d_luts = nullptr;              // [S]
@@ -263,23 +294,59 @@ int64_t cc_ouster_packet_bytes(int rows, int columns_per_packet)
 {
     if (rows < 1 || columns_per_packet < 1)
         return 0;
-    return (int64_t) columns_per_packet * column_bytes(LAYOUT_LEGACY, rows);
+    return packet_bytes_of(LAYOUTS[CC_OUSTER_PROFILE_LEGACY], rows, columns_per_packet);
 }
 
-int cc_ouster_create(cc_ouster** out, int device, int num_streams, int rows, int columns_per_packet, int max_packets, void* hip_stream)
+int64_t cc_ouster_profile_packet_bytes(int profile, int rows, int columns_per_packet)
+{
+    if (profile < 0 || profile >= NUM_PROFILES || rows < 1 || columns_per_packet < 1)
+        return 0;
+    return packet_bytes_of(LAYOUTS[profile], rows, columns_per_packet);
+}
+
+int cc_ouster_profile_from_name(const char* udp_profile_lidar)
+{
+    if (!udp_profile_lidar)
+        return -1;
+    const std::string n = udp_profile_lidar;
+    if (n == "LEGACY")
+        return CC_OUSTER_PROFILE_LEGACY;
+    if (n == "RNG19_RFL8_SIG16_NIR16")
+        return CC_OUSTER_PROFILE_RNG19_RFL8_SIG16_NIR16;
+    if (n == "RNG19_RFL8_SIG16_NIR16_DUAL")
+        return CC_OUSTER_PROFILE_RNG19_RFL8_SIG16_NIR16_DUAL;
+    if (n == "RNG15_RFL8_NIR8" || n == "FUSA_RNG15_RFL8_NIR8_DUAL")
+        return -2; // no SIGNAL field: the reference's ls.field(SIGNAL) cannot run on it
+    return -1;
+}
+
+int cc_ouster_profile_of(cc_ouster* o)
+{
+    return o ? o->profile : -1;
+}
+
+// cc_ouster_create (check_lds false: it has always left a packet beyond the LDS to the launch) and cc_ouster_create_profile.
+static int create_decoder(const std::string& fn, cc_ouster** out, int device, int num_streams, int rows, int columns_per_packet, int max_packets,
+                          int profile, bool check_lds, void* hip_stream)
 {
     if (!out)
-        return fail(CC_ERR_INVALID_ARGUMENT, "cc_ouster_create: null output handle");
+        return fail(CC_ERR_INVALID_ARGUMENT, fn + ": null output handle");
     *out = nullptr;
+    if (profile < 0 || profile >= NUM_PROFILES)
+        return fail(CC_ERR_INVALID_ARGUMENT, fn + ": no UDP profile " + std::to_string(profile) + " (CC_OUSTER_PROFILE_* of cc_ouster_profiles.h)");
     if (num_streams <= 0 || max_packets <= 0)
-        return fail(CC_ERR_INVALID_ARGUMENT, "cc_ouster_create: num_streams and max_packets must be positive");
+        return fail(CC_ERR_INVALID_ARGUMENT, fn + ": num_streams and max_packets must be positive");
     if (rows < 4 || rows > MAX_ROWS || rows % 4 != 0)
-        return fail(CC_ERR_INVALID_ARGUMENT, "cc_ouster_create: rows (pixels_per_column) must be a multiple of 4 in 4.." + std::to_string(MAX_ROWS));
+        return fail(CC_ERR_INVALID_ARGUMENT, fn + ": rows (pixels_per_column) must be a multiple of 4 in 4.." + std::to_string(MAX_ROWS));
     if (columns_per_packet < 1 || columns_per_packet > MAX_COLUMNS_PER_PACKET)
-        return fail(CC_ERR_INVALID_ARGUMENT, "cc_ouster_create: columns_per_packet must be in 1.." + std::to_string(MAX_COLUMNS_PER_PACKET));
+        return fail(CC_ERR_INVALID_ARGUMENT, fn + ": columns_per_packet must be in 1.." + std::to_string(MAX_COLUMNS_PER_PACKET));
+    const int64_t packet_bytes = packet_bytes_of(LAYOUTS[profile], rows, columns_per_packet);
+    if (check_lds && (packet_bytes + 15) / 16 * 16 + (int64_t) (MAX_COLUMNS_PER_PACKET * sizeof(int)) > MAX_LDS_BYTES)
+        return fail(CC_ERR_INVALID_ARGUMENT, fn + ": a packet of " + std::to_string(packet_bytes) + " bytes (" + std::to_string(rows) + " rows x " +
+                                                 std::to_string(columns_per_packet) + " columns) does not fit the 64 KB of LDS it is staged in");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
-        return fail(CC_ERR_NO_DEVICE, "cc_ouster_create: no gfx950 device (there is no CPU variant of this path)");
+        return fail(CC_ERR_NO_DEVICE, fn + ": no gfx950 device (there is no CPU variant of this path)");
     OUSTER_HIP_CHECK(hipSetDevice(device));
     cc_ouster* o = new cc_ouster;
     o->device = device;
@@ -287,7 +354,9 @@ int cc_ouster_create(cc_ouster** out, int device, int num_streams, int rows, int
     o->rows = rows;
     o->columns_per_packet = columns_per_packet;
     o->max_packets = max_packets;
-    o->packet_bytes = (int) cc_ouster_packet_bytes(rows, columns_per_packet);
+    o->packet_bytes = (int) packet_bytes;
+    o->profile = profile;
+    o->layout = resolved(LAYOUTS[profile], rows);
     o->stream_entry.assign(num_streams, -1);
     if (hip_stream)
         o->stream = (hipStream_t) hip_stream;
@@ -302,6 +371,18 @@ int cc_ouster_create(cc_ouster** out, int device, int num_streams, int rows, int
     OUSTER_HIP_CHECK(hipMemset(o->d_counters, 0, (size_t) num_streams * NUM_COUNTERS * sizeof(unsigned long long)));
     *out = o;
     return CC_OK;
+}
+
+int cc_ouster_create(cc_ouster** out, int device, int num_streams, int rows, int columns_per_packet, int max_packets, void* hip_stream)
+{
+    return create_decoder("cc_ouster_create", out, device, num_streams, rows, columns_per_packet, max_packets, CC_OUSTER_PROFILE_LEGACY, false,
+                          hip_stream);
+}
+
+int cc_ouster_create_profile(cc_ouster** out, int device, int num_streams, int rows, int columns_per_packet, int max_packets, int profile,
+                             void* hip_stream)
+{
+    return create_decoder("cc_ouster_create_profile", out, device, num_streams, rows, columns_per_packet, max_packets, profile, true, hip_stream);
 }
 
 void cc_ouster_destroy(cc_ouster* o)
@@ -428,11 +509,11 @@ int cc_ouster_decode(cc_ouster* o, int n_packets, const uint8_t* d_packets, cons
     a.measurement_id = d_measurement_id;
     a.luts = o->d_luts;
     a.counters = o->d_counters;
-    a.L = LAYOUT_LEGACY;
+    a.L = o->layout;
     a.H = o->rows;
     a.C = o->columns_per_packet;
     a.n_packets = n_packets;
-    a.col_bytes = column_bytes(LAYOUT_LEGACY, o->rows);
+    a.col_bytes = column_bytes(o->layout, o->rows);
     a.packet_bytes = o->packet_bytes;
     a.vec16 = ((uintptr_t) d_packets % 16 == 0) && (o->packet_bytes % 16 == 0);
     const size_t lds = (size_t) (o->packet_bytes + 15) / 16 * 16;

@@ -1,8 +1,9 @@
-"""ctypes host mirror of include/cc_ouster.h — Ouster LEGACY lidar packets decoded on the GPU into engine firings.
+"""ctypes host mirror of include/cc_ouster.h and include/cc_ouster_profiles.h — Ouster lidar packets (LEGACY and the RNG19_RFL8_SIG16_NIR16
+single- and dual-return UDP profiles) decoded on the GPU into engine firings.
 
 `OusterDecoder` runs the per-column decode of the reference's OusterInput (ros/ouster_input.hpp:105-181) as a HIP kernel and writes
 the firings in the layout `Engine.add_firings_device` reads; `load_metadata` / `make_lut` turn a sensor metadata JSON into the
-[W][H][3] look-up tables it takes (the SDK's make_xyz_lut, through `cc_ouster_make_lut`). `write_legacy_packets` and
+[W][H][3] look-up tables it takes (the SDK's make_xyz_lut, through `cc_ouster_make_lut`). `write_legacy_packets`, `write_packets` and
 `synthetic_packets` produce packets (no recording is available offline): ranges ray-cast against the synthetic scene of `synth`
 along the LUT's beam directions. No CPU variant of the device decode.
 """
@@ -18,6 +19,17 @@ from . import EngineError, _ptr, load_library, synth
 HEADER_BYTES, PIXEL_BYTES, STATUS_BYTES = 16, 12, 4   # LEGACY column: header, per-pixel block, status word (include/cc_ouster.h)
 RANGE_MASK = 0x000FFFFF
 STATUS_VALID = 0xFFFFFFFF
+
+# UDP profiles: the CC_OUSTER_PROFILE_* enum of include/cc_ouster_profiles.h, indexing PROFILE_NAMES (the metadata's udp_profile_lidar)
+PROFILE_LEGACY, PROFILE_RNG19_RFL8_SIG16_NIR16, PROFILE_RNG19_RFL8_SIG16_NIR16_DUAL = 0, 1, 2
+PROFILE_NAMES = ("LEGACY", "RNG19_RFL8_SIG16_NIR16", "RNG19_RFL8_SIG16_NIR16_DUAL")
+# what the packet writer needs of each profile (the table of include/cc_ouster_profiles.h): packet header (= footer) bytes, column
+# header bytes, pixel bytes, column bytes behind the last pixel, range mask, and the offsets within a pixel of the fields it writes
+_WIRE = (dict(packet_header=0, header=16, pixel=12, trailer=4, range_mask=0x000FFFFF, status_valid=0xFFFFFFFF),
+         dict(packet_header=32, header=12, pixel=12, trailer=0, range_mask=0x0007FFFF, status_valid=0xFFFF,
+              reflectivity=4, signal=6, near_ir=8),
+         dict(packet_header=32, header=12, pixel=16, trailer=0, range_mask=0x0007FFFF, status_valid=0xFFFF,
+              reflectivity=3, range2=4, reflectivity2=7, signal=8, signal2=10, near_ir=12))
 
 _bound = False
 
@@ -41,6 +53,11 @@ def _lib():
         L.cc_ouster_packet_bytes.restype = C.c_int64
         L.cc_ouster_check_engine.argtypes = [vp, vp]
         L.cc_ouster_make_lut.argtypes = [i32, i32, C.c_double, vp, vp, vp, vp, vp]
+        L.cc_ouster_create_profile.argtypes = [C.POINTER(vp), i32, i32, i32, i32, i32, i32, vp]
+        L.cc_ouster_profile_packet_bytes.argtypes = [i32, i32, i32]
+        L.cc_ouster_profile_packet_bytes.restype = C.c_int64
+        L.cc_ouster_profile_from_name.argtypes = [C.c_char_p]
+        L.cc_ouster_profile_of.argtypes = [vp]
         _bound = True
     return L
 
@@ -50,12 +67,29 @@ def _check(rc: int):
         raise EngineError(rc, _lib().cc_ouster_last_error().decode())
 
 
-def column_bytes(rows: int) -> int:
-    return HEADER_BYTES + PIXEL_BYTES * rows + STATUS_BYTES
+def profile_id(profile) -> int:
+    """The CC_OUSTER_PROFILE_* enum of a udp_profile_lidar name or of the enum itself. ValueError for a profile without a SIGNAL field
+    (RNG15_RFL8_NIR8, FUSA_RNG15_RFL8_NIR8_DUAL) and for an unknown one."""
+    if isinstance(profile, str):
+        p = int(_lib().cc_ouster_profile_from_name(profile.encode()))
+        if p == -2:
+            raise ValueError(f"udp_profile_lidar {profile} has no SIGNAL field: the reference cannot run this profile")
+        if p < 0:
+            raise ValueError(f"udp_profile_lidar {profile} is unknown (supported: {', '.join(PROFILE_NAMES)})")
+        return p
+    p = int(profile)
+    if not 0 <= p < len(PROFILE_NAMES):
+        raise ValueError(f"no UDP profile {profile} (supported: 0..{len(PROFILE_NAMES) - 1}, {', '.join(PROFILE_NAMES)})")
+    return p
 
 
-def packet_bytes(rows: int, columns_per_packet: int) -> int:
-    return int(_lib().cc_ouster_packet_bytes(rows, columns_per_packet))
+def column_bytes(rows: int, profile="LEGACY") -> int:
+    w = _WIRE[profile_id(profile)]
+    return w["header"] + w["pixel"] * rows + w["trailer"]
+
+
+def packet_bytes(rows: int, columns_per_packet: int, profile="LEGACY") -> int:
+    return int(_lib().cc_ouster_profile_packet_bytes(profile_id(profile), rows, columns_per_packet))
 
 
 # ---- metadata and look-up table ----------------------------------------------------------------------------------------------
@@ -64,20 +98,26 @@ def load_metadata(path: str) -> dict:
     """The fields of an Ouster metadata JSON the decode needs (the reference reads it with metadata_from_json, ouster_input.hpp:58)."""
     with open(path) as f:
         j = json.load(f)
-    fmt = j["data_format"]
-    if fmt.get("udp_profile_lidar", "LEGACY") != "LEGACY":
-        raise ValueError(f"{path}: udp_profile_lidar {fmt['udp_profile_lidar']} is not supported (LEGACY only)")
+    # the flat layout, or the newer nested one: lidar_data_format, beam_intrinsics, lidar_intrinsics
+    fmt = j["lidar_data_format"] if "lidar_data_format" in j else j["data_format"]
+    beam, lidar = j.get("beam_intrinsics", j), j.get("lidar_intrinsics", j)
+    name = fmt.get("udp_profile_lidar", "LEGACY")
+    try:
+        profile_id(name)
+    except ValueError as e:
+        raise ValueError(f"{path}: {e}") from None
     return dict(rows=int(fmt["pixels_per_column"]), columns_per_frame=int(fmt["columns_per_frame"]),
-                columns_per_packet=int(fmt["columns_per_packet"]),
-                lidar_origin_to_beam_origin_mm=float(j["lidar_origin_to_beam_origin_mm"]),
-                lidar_to_sensor_transform=np.asarray(j["lidar_to_sensor_transform"], dtype=np.float64).reshape(16),
-                beam_azimuth_angles=np.asarray(j["beam_azimuth_angles"], dtype=np.float64),
-                beam_altitude_angles=np.asarray(j["beam_altitude_angles"], dtype=np.float64))
+                columns_per_packet=int(fmt["columns_per_packet"]), udp_profile_lidar=name,
+                lidar_origin_to_beam_origin_mm=float(beam["lidar_origin_to_beam_origin_mm"]),
+                lidar_to_sensor_transform=np.asarray(lidar["lidar_to_sensor_transform"], dtype=np.float64).reshape(16),
+                beam_azimuth_angles=np.asarray(beam["beam_azimuth_angles"], dtype=np.float64),
+                beam_altitude_angles=np.asarray(beam["beam_altitude_angles"], dtype=np.float64))
 
 
-def synthetic_metadata(rows: int = 64, columns_per_frame: int = 2048, columns_per_packet: int = 16) -> dict:
-    """Metadata of a made-up LEGACY sensor (altitudes evenly spread over +-22.5 degrees, a small azimuth stagger per beam)."""
-    return dict(rows=rows, columns_per_frame=columns_per_frame, columns_per_packet=columns_per_packet,
+def synthetic_metadata(rows: int = 64, columns_per_frame: int = 2048, columns_per_packet: int = 16, udp_profile_lidar: str = "LEGACY") -> dict:
+    """Metadata of a made-up sensor (altitudes evenly spread over +-22.5 degrees, a small azimuth stagger per beam)."""
+    profile_id(udp_profile_lidar)
+    return dict(rows=rows, columns_per_frame=columns_per_frame, columns_per_packet=columns_per_packet, udp_profile_lidar=udp_profile_lidar,
                 lidar_origin_to_beam_origin_mm=15.8,
                 lidar_to_sensor_transform=np.array([-1, 0, 0, 0, 0, -1, 0, 0, 0, 0, 1, 38.195, 0, 0, 0, 1], dtype=np.float64),
                 beam_azimuth_angles=np.array([(3.0 if r % 4 < 2 else -3.0) + 0.1 * (r % 2) for r in range(rows)], dtype=np.float64),
@@ -105,18 +145,24 @@ def make_lut(meta: dict, offset: str = "reference"):
 # ---- device decode -----------------------------------------------------------------------------------------------------------
 
 class OusterDecoder:
-    """One cc_ouster handle: `num_streams` sensors of `rows` beams, up to `max_packets` packets per stream and call. Pass
-    hip_stream=engine.hip_stream() (and set the engine option "input_on_engine_stream") to chain the decode with an engine; close the
-    decoder before that engine."""
+    """One cc_ouster handle: `num_streams` sensors of `rows` beams and one UDP `profile` (a udp_profile_lidar name or the enum), up to
+    `max_packets` packets per stream and call. Pass hip_stream=engine.hip_stream() (and set the engine option "input_on_engine_stream")
+    to chain the decode with an engine; close the decoder before that engine."""
 
     def __init__(self, num_streams: int, rows: int, columns_per_packet: int = 16, max_packets: int = 64, device: int = 0,
-                 hip_stream: int | None = None):
+                 hip_stream: int | None = None, profile="LEGACY"):
         self.L = _lib()
         self.num_streams, self.rows, self.columns_per_packet, self.max_packets = num_streams, rows, columns_per_packet, max_packets
         self.device = device
-        self.packet_bytes = packet_bytes(rows, columns_per_packet)
+        self.profile = profile_id(profile)
+        self.profile_name = PROFILE_NAMES[self.profile]
+        self.packet_bytes = packet_bytes(rows, columns_per_packet, self.profile)
         self.h = C.c_void_p()
-        rc = self.L.cc_ouster_create(C.byref(self.h), device, num_streams, rows, columns_per_packet, max_packets, hip_stream)
+        if self.profile == PROFILE_LEGACY:
+            rc = self.L.cc_ouster_create(C.byref(self.h), device, num_streams, rows, columns_per_packet, max_packets, hip_stream)
+        else:
+            rc = self.L.cc_ouster_create_profile(C.byref(self.h), device, num_streams, rows, columns_per_packet, max_packets, self.profile,
+                                                 hip_stream)
         if rc != 0:
             self.h = None
             _check(rc)
@@ -160,7 +206,7 @@ class OusterDecoder:
         S, P = self.num_streams, int(packets.shape[1])
         n = P * self.columns_per_packet
         if tuple(packets.shape) != (S, P, self.packet_bytes) or packets.dtype != torch.uint8 or not packets.is_contiguous():
-            raise ValueError(f"packets must be a contiguous uint8 tensor [{S}][P][{self.packet_bytes}]")
+            raise ValueError(f"packets must be a contiguous uint8 tensor [{S}][P][{self.packet_bytes}] ({self.profile_name} packets)")
         if packet_poses is not None and (tuple(packet_poses.shape) != (S, P, 12) or packet_poses.dtype != torch.float64
                                          or not packet_poses.is_contiguous()):
             raise ValueError(f"packet_poses must be a contiguous float64 tensor [{S}][{P}][12]")
@@ -233,15 +279,69 @@ def write_legacy_packets(ranges, signal, m_ids, status=None, timestamps=None, fr
     return cols.reshape(*lead, Cc * column_bytes(H))
 
 
+def write_packets(profile, ranges, signal, m_ids, status=None, timestamps=None, frame_id=None, encoder=None, reflectivity=None, near_ir=None,
+                  range2=None, signal2=None, reflectivity2=None, header=None, footer=None) -> np.ndarray:
+    """Packets of `profile` (a name or the enum) from per-pixel arrays [..., P, C, H] (ranges, range2: the raw u32 word, the bits the
+    profile's range mask removes included) and per-column arrays [..., P, C] (status default: all bits set = valid). LEGACY is
+    write_legacy_packets. The RNG19 profiles have a 32-byte packet header and footer: `header` / `footer` uint8 [..., P, 32] are copied
+    in as they are (default zeros, with frame_id as the u16 at header byte 2); `encoder` exists in LEGACY only. The 8-bit reflectivity
+    is written after the range word, so in the dual profile (byte 3) it replaces that word's top byte; range2, signal2 and
+    reflectivity2 (pixel byte 7, the top byte of the range2 word) exist in the dual profile only.
+    Returns uint8 [..., P, packet_bytes]."""
+    prof = profile_id(profile)
+    if prof == PROFILE_LEGACY:
+        if any(x is not None for x in (range2, signal2, reflectivity2, header, footer)):
+            raise ValueError("LEGACY packets have no second return and no packet header or footer")
+        return write_legacy_packets(ranges, signal, m_ids, status, timestamps, frame_id, encoder, reflectivity, near_ir)
+    w = _WIRE[prof]
+    if prof != PROFILE_RNG19_RFL8_SIG16_NIR16_DUAL and any(x is not None for x in (range2, signal2, reflectivity2)):
+        raise ValueError(f"{PROFILE_NAMES[prof]} packets have no second return")
+    if encoder is not None:
+        raise ValueError(f"{PROFILE_NAMES[prof]} columns have no encoder count")
+    ranges = np.asarray(ranges)
+    *lead, Cc, H = ranges.shape
+    hb, pb, ph = w["header"], w["pixel"], w["packet_header"]
+    cb = hb + pb * H + w["trailer"]
+    pk = np.zeros((*lead, ph + Cc * cb + ph), dtype=np.uint8)
+    cols = pk[..., ph:ph + Cc * cb].reshape(*lead, Cc, cb)                       # views into pk
+    px = cols[..., hb:hb + pb * H].reshape(*lead, Cc, H, pb)
+
+    def put(dst, shape, arr, off, dt):
+        if arr is None:
+            return
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(arr), shape).astype(dt))
+        dst[..., off:off + np.dtype(dt).itemsize] = a[..., None].view(np.uint8)
+
+    put(cols, cols.shape[:-1], 0 if timestamps is None else timestamps, 0, "<u8")
+    put(cols, cols.shape[:-1], m_ids, 8, "<u2")
+    put(cols, cols.shape[:-1], w["status_valid"] if status is None else status, 10, "<u2")
+    put(px, ranges.shape, ranges, 0, "<u4")
+    put(px, ranges.shape, range2, w.get("range2", 0), "<u4")
+    put(px, ranges.shape, reflectivity, w["reflectivity"], "u1")
+    put(px, ranges.shape, reflectivity2, w.get("reflectivity2", 0), "u1")
+    put(px, ranges.shape, signal, w["signal"], "<u2")
+    put(px, ranges.shape, signal2, w.get("signal2", 0), "<u2")
+    put(px, ranges.shape, near_ir, w["near_ir"], "<u2")
+    if header is not None:
+        pk[..., :ph] = np.asarray(header, dtype=np.uint8)
+    elif frame_id is not None:
+        put(pk, pk.shape[:-1], np.broadcast_to(np.asarray(frame_id), cols.shape[:-1])[..., 0], 2, "<u2")   # its first column's
+    if footer is not None:
+        pk[..., ph + Cc * cb:] = np.asarray(footer, dtype=np.uint8)
+    return pk
+
+
 def synthetic_packets(meta: dict, n_packets: int, seed: int = 0, first_packet: int = 0, motion: synth.Motion | None = None,
                       scene: synth.SceneModel | None = None, rotation_hz: float = 10.0) -> dict:
     """`n_packets` consecutive packets of a sensor described by `meta`, starting at packet `first_packet` after power-up: ranges are
     ray-cast against the synthetic scene of synth (ground, cylinders, wall ring) along the LUT's beam directions from a sensor moving
-    with `motion`. Returns dict(packets uint8 [P][bytes], packet_poses float64 [P][12] (odom_from_sensor at the packet's first column),
+    with `motion`. The packets are of the UDP profile `meta` names (LEGACY when it names none), ranges clipped to that profile's range
+    mask. Returns dict(packets uint8 [P][bytes], packet_poses float64 [P][12] (odom_from_sensor at the packet's first column),
     ranges uint32 [P][C][H], signal uint16 [P][C][H], m_ids [P][C], status [P][C])."""
     motion = motion or synth.Motion.static()
     scene = scene or synth.SceneModel()
     H, W, Cc = meta["rows"], meta["columns_per_frame"], meta["columns_per_packet"]
+    prof = profile_id(meta.get("udp_profile_lidar", "LEGACY"))
     direction, _ = make_lut(meta, "sdk")
     unit = direction.astype(np.float64)
     unit /= np.linalg.norm(unit, axis=-1, keepdims=True)
@@ -270,13 +370,13 @@ def synthetic_packets(meta: dict, n_packets: int, seed: int = 0, first_packet: i
     drop = rng.uniform(0, 1, (F, H)) < scene.dropout
     noise = rng.uniform(-scene.range_noise, scene.range_noise, (F, H))
     valid = (t < scene.max_range) & ~drop
-    rng_mm = np.where(valid, np.clip(np.rint((np.where(valid, t, 0.0) + noise) * 1000.0), 1, RANGE_MASK), 0).astype(np.uint32)
+    rng_mm = np.where(valid, np.clip(np.rint((np.where(valid, t, 0.0) + noise) * 1000.0), 1, _WIRE[prof]["range_mask"]), 0).astype(np.uint32)
     ranges = rng_mm.reshape(n_packets, Cc, H)
     signal = rng.integers(0, 1400, (n_packets, Cc, H), dtype=np.uint16)
-    status = np.full((n_packets, Cc), STATUS_VALID, dtype=np.uint32)
+    status = np.full((n_packets, Cc), _WIRE[prof]["status_valid"], dtype=np.uint32)
     stamps = (tsec * 1e9).astype(np.uint64)
-    packets = write_legacy_packets(ranges, signal, m_ids, status, timestamps=stamps, frame_id=(j // W).astype(np.uint16),
-                                   encoder=(m_ids.astype(np.uint32) * (90112 // W)))
+    packets = write_packets(prof, ranges, signal, m_ids, status, timestamps=stamps, frame_id=(j // W).astype(np.uint16),
+                            encoder=(m_ids.astype(np.uint32) * (90112 // W)) if prof == PROFILE_LEGACY else None)
     yaw0, px0, py0, pz0 = pose_at(tsec[:, 0])
     c, s = np.cos(yaw0), np.sin(yaw0)
     z = np.zeros_like(c)
@@ -289,5 +389,6 @@ def rotation_packets(meta: dict) -> int:
     return meta["columns_per_frame"] // meta["columns_per_packet"]
 
 
-__all__ = ["OusterDecoder", "load_metadata", "make_lut", "synthetic_metadata", "write_legacy_packets", "synthetic_packets",
-           "packet_bytes", "column_bytes", "rotation_packets", "RANGE_MASK", "STATUS_VALID"]
+__all__ = ["OusterDecoder", "load_metadata", "make_lut", "synthetic_metadata", "write_legacy_packets", "write_packets", "synthetic_packets",
+           "packet_bytes", "column_bytes", "rotation_packets", "profile_id", "RANGE_MASK", "STATUS_VALID", "PROFILE_NAMES", "PROFILE_LEGACY",
+           "PROFILE_RNG19_RFL8_SIG16_NIR16", "PROFILE_RNG19_RFL8_SIG16_NIR16_DUAL"]

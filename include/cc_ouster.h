@@ -5,6 +5,10 @@
  * writes the firings straight into the arrays cc_engine_add_firings_device (cc_hip.h) consumes, so packets go to HBM once and
  * never come back to the host. There is no CPU variant of the device path: cc_ouster_create fails with CC_ERR_NO_DEVICE without a GPU.
  *
+ * cc_ouster_create makes a decoder of the LEGACY UDP profile, laid out below. The RNG19_RFL8_SIG16_NIR16 single- and dual-return profiles
+ * (cc_ouster_create_profile and the other profile functions) are declared in cc_ouster_profiles.h; a handle made there works with every
+ * function of this header, and what a column produces is the same for every profile.
+ *
  * Packet layout, LEGACY UDP profile (all fields little-endian, no packet header or footer; H = pixels_per_column,
  * C = columns_per_packet). Restated from the Ouster SDK's packet_format, which is not a dependency: UNPINNED.
  *
@@ -64,7 +68,8 @@ void* cc_ouster_hip_stream(cc_ouster* o);
 int cc_ouster_set_lut(cc_ouster* o, int stream, int columns_per_frame, const float* direction, const float* offset);
 
 /* Decode n_packets packets of every stream (asynchronous, on the handle's HIP stream). DEVICE pointers:
- *   d_packets         [S][n_packets][packet_bytes]  raw packets (4-byte aligned; 16-byte alignment lets the kernel use 16-B loads)
+ *   d_packets         [S][n_packets][packet_bytes]  raw packets of the handle's profile (4-byte aligned; 16-byte alignment and a packet size
+ *                                                   that is a multiple of 16 let the kernel use 16-B loads)
  *   d_packet_poses    [S][n_packets][12] doubles    odom_from_sensor of each packet, replicated to its C firings (:111: every firing of a
  *                                                   packet carries the packet's receive stamp); NULL = d_poses is left as the caller wrote it
  *   d_skip            [S][n_packets] uint8          nonzero: every column of the packet becomes an all-NaN firing; NULL = none
