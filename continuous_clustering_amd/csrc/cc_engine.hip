@@ -154,6 +154,7 @@ struct cc_engine
     bool assoc_waves_auto{true};        // ... 0 (default): k_assoc3, links wavefront while a launch has at most 256 streams
     bool assoc_pending[4]{false, false, false, false};
     std::vector<void*> allocations;
+    std::vector<std::pair<void**, int>> pinned; // every pinned host block: where its pointer lives, PinnedLifetime (cc_buffers.h)
     // the chains of the last batch behind its insertion, not launched yet (launch_batch). With the lazy gate the closure first WAITS for that
     // insertion and reads its counters; `redo` (may be null) launches the next batch's insertion again when those counters say that the one
     // enqueued ahead of them was turned into a no-op
@@ -182,7 +183,7 @@ struct cc_engine
     // staging of k_prep: [streams in launch][n][rows]
     size_t prep_capacity{0};
     // staging for cc_engine_read_columns
-    void* d_view{nullptr};
+    char* d_view{nullptr};
     size_t view_bytes{0};
     double* d_ego[4]{nullptr, nullptr, nullptr, nullptr}; // k_ego output per batch-descriptor slot: [streams in launch][n][12]
     size_t ego_capacity{0};
@@ -259,6 +260,8 @@ int alloc_plane(cc_engine* e, T** out, size_t count)
     return CC_OK;
 }
 
+#include "cc_buffers.h" // the grow-only scratch, the pinned host blocks, the lists of streams and events
+
 int validate(cc_engine* e, const cc_config* cfg, int num_rows, int num_streams)
 {
     if (!cfg || num_rows < 1 || num_rows > WAVE * MAX_ROWS_PER_LANE || num_streams < 1 || cfg->num_columns < 4 ||
@@ -309,33 +312,10 @@ int free_all(cc_engine* e)
     e->d_small = nullptr;
     e->d_small_seq = nullptr; // (freed with the allocations above; the pinned counter below goes with it)
     e->d_input_sum = nullptr;
-    if (e->h_res_ctl)
-        (void) hipHostFree(e->h_res_ctl);
-    e->h_res_ctl = nullptr;
-    if (e->h_small_view_hdr)
-        (void) hipHostFree(e->h_small_view_hdr);
-    if (e->h_small_view)
-        (void) hipHostFree(e->h_small_view);
-    e->h_small_view_hdr = nullptr;
-    e->h_small_view = nullptr;
     e->small_view_ok = false;
-    if (e->h_input_sum)
-        (void) hipHostFree(e->h_input_sum);
-    e->h_input_sum = nullptr;
     e->small_seq_expected = 0;
-    // the pinned staging of the small-call path is sized for the row count it was created with
-    if (e->h_small)
-    {
-        (void) hipHostFree(e->h_small);
-        (void) hipHostFree(e->h_small_state);
-        (void) hipHostFree(e->h_small_events);
-        if (e->h_small_seq)
-            (void) hipHostFree(e->h_small_seq);
-        e->h_small_seq = nullptr;
-        e->h_small = nullptr;
-        e->h_small_state = nullptr;
-        e->h_small_events = nullptr;
-    }
+    // the pinned staging of the small-call path is sized for the row count it was created with; the mirrored counters go with the device blocks above
+    free_pinned(e, PIN_SHAPE);
     return CC_OK;
 }
 
@@ -706,12 +686,11 @@ int sync_all(cc_engine* e)
         if (rcs)
             return rcs;
     }
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream));
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream2));
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream3));
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream4));
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream5));
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream6));
+    {
+        int rcs = sync_streams(e);
+        if (rcs)
+            return rcs;
+    }
     for (bool& b : e->assoc_pending)
         b = false;
     e->idle = true;
@@ -740,9 +719,8 @@ static int input_sum(cc_engine* e, const cc_engine::InputRec& r, unsigned long l
 {
     if (!e->h_input_sum)
     {
-        CC_HIP_CHECK(e, hipHostMalloc((void**) &e->h_input_sum, 64));
-        int rca = alloc_plane(e, &e->d_input_sum, 8);
-        if (rca)
+        int rca = alloc_pinned(e, &e->h_input_sum, 64, PIN_SHAPE);
+        if (rca || (rca = alloc_plane(e, &e->d_input_sum, 8)))
             return rca;
     }
     CC_HIP_CHECK(e, hipMemsetAsync(e->d_input_sum, 0, sizeof(unsigned long long), e->stream));
@@ -1087,30 +1065,21 @@ int add_firings_small(cc_engine* e, int stream, int64_t n, const float* xyz, con
     const int R = e->g.num_rows;
     const size_t b_xyz = (size_t) SMALL_STAGE * R * 3 * sizeof(float), b_int = (((size_t) SMALL_STAGE * R) + 15) & ~(size_t) 15,
                  b_pose = (size_t) SMALL_STAGE * 12 * sizeof(double);
-    if (e->h_small && !e->d_small && alloc_plane(e, &e->d_small, b_xyz + b_int + b_pose) != CC_OK)
-        return -1;
-    if (!e->h_small)
+    // the four pinned blocks of the staging are there together or not at all: a call never goes on with part of them
+    if (!e->h_small && (alloc_pinned(e, &e->h_small, b_xyz + b_int + b_pose, PIN_SHAPE) || alloc_pinned(e, &e->h_small_seq, 64, PIN_SHAPE) ||
+                        alloc_pinned(e, &e->h_small_state, sizeof(StreamState), PIN_SHAPE) ||
+                        alloc_pinned(e, &e->h_small_events, SMALL_EVENTS * sizeof(cc_event), PIN_SHAPE)))
     {
-        if (hipHostMalloc((void**) &e->h_small, b_xyz + b_int + b_pose) != hipSuccess ||
-            hipHostMalloc((void**) &e->h_small_seq, 64) != hipSuccess ||
-            hipHostMalloc((void**) &e->h_small_state, sizeof(StreamState)) != hipSuccess ||
-            hipHostMalloc((void**) &e->h_small_events, SMALL_EVENTS * sizeof(cc_event)) != hipSuccess)
-            return -1;
-        int rc = alloc_plane(e, &e->d_small, b_xyz + b_int + b_pose);
-        if (rc)
-            return -1;
+        release_pinned(&e->h_small), release_pinned(&e->h_small_seq), release_pinned(&e->h_small_state), release_pinned(&e->h_small_events);
+        return -1;
     }
+    if (!e->d_small && alloc_plane(e, &e->d_small, b_xyz + b_int + b_pose) != CC_OK)
+        return -1;
     const float* d_xyz = (const float*) e->d_small;
     const uint8_t* d_int = e->d_small + b_xyz;
     const double* d_pose = (const double*) (e->d_small + b_xyz + b_int);
-    if (e->ego_capacity < 4096)
-    {
-        for (int i = 0; i < 4; i++)
-            if (alloc_plane(e, &e->d_ego[i], (size_t) 4096 * cck::EGO_STRIDE) != CC_OK)
-                return -1;
-        e->ego_capacity = 4096;
-        e->small_graphs_stale = true;
-    }
+    if (ensure_ego(e, 4096) != CC_OK)
+        return -1;
     if (e->small_graphs_stale)
     {
         destroy_small_graphs(e);
@@ -1149,8 +1118,11 @@ int add_firings_small(cc_engine* e, int stream, int64_t n, const float* xyz, con
     {
         size_t vbytes = 0;
         (void) cck::view_layout(nullptr, (size_t) cck::MV_COLS * R, &vbytes);
-        if (!e->h_small_view_hdr && (hipHostMalloc((void**) &e->h_small_view_hdr, 256) != hipSuccess || hipHostMalloc((void**) &e->h_small_view, vbytes + 64) != hipSuccess))
+        if (!e->h_small_view_hdr && (alloc_pinned(e, &e->h_small_view_hdr, 256, PIN_SHAPE) || alloc_pinned(e, &e->h_small_view, vbytes + 64, PIN_SHAPE)))
+        {
+            release_pinned(&e->h_small_view_hdr), release_pinned(&e->h_small_view); // (both or neither, like the staging)
             return -1;
+        }
         void *a = nullptr, *b = nullptr;
         if (hipHostGetDevicePointer(&a, e->h_small_view_hdr, 0) == hipSuccess && hipHostGetDevicePointer(&b, e->h_small_view, 0) == hipSuccess)
             zvh = (long long*) a, zvb = (char*) b;
@@ -1244,7 +1216,9 @@ int add_firings_small(cc_engine* e, int stream, int64_t n, const float* xyz, con
     {
         if (!e->h_res_ctl)
         {
-            CC_HIP_CHECK(e, hipHostMalloc((void**) &e->h_res_ctl, sizeof(cck::ResidentCtl)));
+            int rca = alloc_pinned(e, &e->h_res_ctl, sizeof(cck::ResidentCtl), PIN_SHAPE);
+            if (rca)
+                return rca;
             memset(e->h_res_ctl, 0, sizeof(cck::ResidentCtl));
         }
         void* zc = nullptr;
@@ -1486,6 +1460,35 @@ void give_back_streams(cc_engine* e)
     release_stream_set(e->device, StreamSet{{e->stream, e->stream2, e->stream3, e->stream4, e->stream5, e->stream6}});
     e->stream = e->stream2 = e->stream3 = e->stream4 = e->stream5 = e->stream6 = nullptr;
 }
+// option "forget_inclination_table": sc_inclination_angles_between_lasers_ as a freshly constructed object has it (cc_engine_reset keeps it, like the
+// reference's resize does): for callers that ran made-up data through a new engine (the drop-in class's warm-up)
+int forget_inclination_table(cc_engine* e)
+{
+    CC_HIP_CHECK(e, hipMemset(e->P.curtab, 0xFF, (size_t) e->g.num_streams * (size_t) e->g.num_rows * sizeof(float)));
+    return CC_OK;
+}
+
+// option "prewarm_small_graphs". Capturing and instantiating the graph of a call size takes milliseconds, once per size: a front-end that feeds a
+// live sensor pays them here (the drop-in class does, in reset()), not in front of the first call of every size — with the asynchronous mode handing
+// the engine whatever has queued up (1 .. 8 firings), eight such stalls of up to 30 ms each sat inside the first seconds of a stream.
+// Best effort: a buffer that cannot be had now is asked for again by the call that needs it.
+void prewarm_small_calls(cc_engine* e)
+{
+    if (e->g.num_streams != 1)
+        return;
+    // buffers first, sized for the largest call the drop-in class makes (a rotation of firings, when its caller ran ahead): growing them later
+    // re-allocates what the captured graphs point at, i.e. drops the graphs again
+    (void) ensure_ego(e, (size_t) std::max(4096, e->g.num_columns));
+    (void) ensure_prep(e, (size_t) e->g.num_columns * (size_t) e->g.num_rows);
+    // the scratch of cc_engine_read_columns (a mirror reads a few columns per call: 512 columns of every field) and of
+    // cc_engine_gather_cluster_points: a pinned allocation in front of the first finished cluster is a stall of milliseconds
+    (void) ensure_view(e, (size_t) 512 * e->g.num_rows * (5 * 4 + 8 + 3 * 8 + 3 + 8 + 4 + 8 + 8 + 5 * 4 + 1) + 256);
+    (void) ensure_gather(e, (size_t) 4 << 20, 1);
+    for (int64_t k = 1; k <= SMALL_MAX; k++)
+        (void) add_firings_small(e, 0, k, nullptr, nullptr, nullptr);
+}
+
+#include "cc_options.h" // the table behind cc_engine_set_option
 } // namespace
 
 extern "C" {
@@ -1562,21 +1565,7 @@ int cc_engine_create(cc_engine** out, int device, int num_streams, int num_rows,
         return CC_ERR_HIP;
     }
     e->stream = set.s[0], e->stream2 = set.s[1], e->stream3 = set.s[2], e->stream4 = set.s[3], e->stream5 = set.s[4], e->stream6 = set.s[5];
-    for (int i = 0; i < 4; i++)
-    {
-        (void) hipEventCreateWithFlags(&e->ev_ins[i], hipEventDisableTiming);
-        (void) hipEventCreateWithFlags(&e->ev_gate[i], hipEventDisableTiming);
-        (void) hipEventCreateWithFlags(&e->ev_seg[i], hipEventDisableTiming);
-        (void) hipEventCreateWithFlags(&e->ev_assoc[i], hipEventDisableTiming);
-        (void) hipEventCreateWithFlags(&e->ev_segscan[i], hipEventDisableTiming);
-        (void) hipEventCreateWithFlags(&e->ev_prep[i], hipEventDisableTiming);
-        (void) hipEventCreateWithFlags(&e->ev_pubrdy[i], hipEventDisableTiming);
-        (void) hipEventCreateWithFlags(&e->ev_rel[i], hipEventDisableTiming);
-        (void) hipEventCreateWithFlags(&e->ev_rel[i + 4], hipEventDisableTiming);
-        if (i == 0)
-            (void) hipEventCreateWithFlags(&e->ev_input, hipEventDisableTiming);
-
-    }
+    for_each_event(e, [](hipEvent_t& ev) { (void) hipEventCreateWithFlags(&ev, hipEventDisableTiming); });
     e->cfg = *cfg;
     e->g.num_streams = num_streams;
     e->g.tree_capacity = 1 << 15;
@@ -1599,18 +1588,18 @@ int cc_engine_create(cc_engine** out, int device, int num_streams, int num_rows,
     (void) hipFuncSetAttribute((const void*) (cck::k_insert_par<1, cck::IP_WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
     (void) hipFuncSetAttribute((const void*) (cck::k_insert_par<1, 2 * cck::IP_WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
     rc = allocate(e);
-    if (rc == CC_OK && hipHostMalloc((void**) &e->h_par_left, 8 * sizeof(int)) != hipSuccess)
-        rc = CC_ERR_HIP;
+    if (rc == CC_OK)
+        rc = alloc_pinned(e, &e->h_par_left, 8 * sizeof(int), PIN_ENGINE);
     {
         const char* hp = std::getenv("CC_HOST_PROF");
         e->host_prof = hp && hp[0] == '1';
     }
-    if (rc == CC_OK && hipHostMalloc((void**) &e->h_bail_count, 4 * sizeof(int)) != hipSuccess)
-        rc = CC_ERR_HIP;
+    if (rc == CC_OK)
+        rc = alloc_pinned(e, &e->h_bail_count, 4 * sizeof(int), PIN_ENGINE);
     if (rc == CC_OK)
         e->h_bail_count[0] = e->h_bail_count[1] = e->h_bail_count[2] = e->h_bail_count[3] = 0;
-    if (rc == CC_OK && hipHostMalloc((void**) &e->h_remaining, sizeof(int)) != hipSuccess)
-        rc = CC_ERR_HIP;
+    if (rc == CC_OK)
+        rc = alloc_pinned(e, &e->h_remaining, sizeof(int), PIN_ENGINE);
     if (rc == CC_OK)
     {
         *e->h_remaining = 0;
@@ -1620,12 +1609,7 @@ int cc_engine_create(cc_engine** out, int device, int num_streams, int num_rows,
     {
         fprintf(stderr, "cc_engine_create: %s\n", e->error.c_str());
         free_all(e);
-        if (e->h_remaining)
-            (void) hipHostFree(e->h_remaining);
-        if (e->h_par_left)
-            (void) hipHostFree(e->h_par_left);
-        if (e->h_bail_count)
-            (void) hipHostFree(e->h_bail_count);
+        free_pinned(e, PIN_ENGINE);
         give_back_streams(e);
         delete e;
         return rc;
@@ -1655,42 +1639,21 @@ void cc_engine_destroy(cc_engine* e)
     if (e->host_prof && e->hp_calls > 0)
         fprintf(stderr, "[cc host_prof] gated calls %lld: entry->launch_batch %.1f us, launch_batch->gate %.1f us, gate wait %.1f us, gate->return %.1f us (per call)\n",
                 e->hp_calls, e->hp_entry / e->hp_calls * 1e6, e->hp_pre / e->hp_calls * 1e6, e->hp_gate / e->hp_calls * 1e6, e->hp_post / e->hp_calls * 1e6);
-    (void) hipStreamSynchronize(e->stream);
-    (void) hipStreamSynchronize(e->stream2);
-    (void) hipStreamSynchronize(e->stream3);
-    (void) hipStreamSynchronize(e->stream4);
-    (void) hipStreamSynchronize(e->stream6);
-    (void) hipStreamSynchronize(e->stream5);
+    (void) for_each_stream(e, [](hipStream_t s) -> int
+    {
+        (void) hipStreamSynchronize(s);
+        return CC_OK;
+    });
     e->deferred_tail = nullptr; // (chains a pipelined call left to "the next call": there is none)
     e->lazy_pending = false;
     destroy_small_graphs(e);
     free_all(e); // also the pinned small-call staging
-    if (e->h_view)
-        (void) hipHostFree(e->h_view);
-    for (int i = 0; i < 4; i++)
-    {
-        (void) hipEventDestroy(e->ev_ins[i]);
-        (void) hipEventDestroy(e->ev_gate[i]);
-        (void) hipEventDestroy(e->ev_seg[i]);
-        (void) hipEventDestroy(e->ev_assoc[i]);
-        (void) hipEventDestroy(e->ev_segscan[i]);
-        (void) hipEventDestroy(e->ev_prep[i]);
-        (void) hipEventDestroy(e->ev_pubrdy[i]);
-        (void) hipEventDestroy(e->ev_rel[i]);
-        (void) hipEventDestroy(e->ev_rel[i + 4]);
-        if (i == 0)
-            (void) hipEventDestroy(e->ev_input);
-    }
+    free_pinned(e, PIN_ENGINE);
+    for_each_event(e, [](hipEvent_t& ev) { (void) hipEventDestroy(ev); });
     for (hipEvent_t ev : e->pev_pool)
         (void) hipEventDestroy(ev);
     for (hipEvent_t ev : e->ev_pool)
         (void) hipEventDestroy(ev);
-    if (e->h_remaining)
-        (void) hipHostFree(e->h_remaining);
-    if (e->h_par_left)
-        (void) hipHostFree(e->h_par_left);
-    if (e->h_bail_count)
-        (void) hipHostFree(e->h_bail_count);
     give_back_streams(e);
     delete e;
 }
@@ -1751,12 +1714,9 @@ int cc_engine_reset(cc_engine* e, int num_rows)
     rc = flush_deferred(e);
     if (rc)
         return rc;
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream));
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream2));
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream3));
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream4));
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream5));
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream6));
+    rc = sync_streams(e);
+    if (rc)
+        return rc;
     e->batch_open = false;
     e->idle = true;
     rc = note_released(e, e->call_seq); // (nothing of the old epoch reads the callers' buffers any more)
@@ -2108,24 +2068,9 @@ static int read_ranges(cc_engine* e, int stream, int nr, const int64_t* from, co
     size_t used = 0;
     (void) cck::view_layout(nullptr, n, &used);
     const size_t bytes = used + 256;
-    if (e->view_bytes < bytes)
-    {
-        void* p = nullptr;
-        CC_HIP_CHECK(e, hipMalloc(&p, bytes));
-        e->allocations.push_back(p);
-        e->d_view = p;
-        e->view_bytes = bytes;
-    }
-    if (e->h_view_bytes < bytes)
-    {
-        if (e->h_view)
-            (void) hipHostFree(e->h_view);
-        e->h_view = nullptr;
-        e->h_view_bytes = 0;
-        CC_HIP_CHECK(e, hipHostMalloc((void**) &e->h_view, bytes));
-        e->h_view_bytes = bytes;
-    }
-    char* base = (char*) e->d_view;
+    if ((rc = ensure_view(e, bytes)))
+        return rc;
+    char* base = e->d_view;
     cck::ViewOut o = cck::view_layout(base, n);
     char* const nchild_at = (char*) o.nchild;
     // the optional fields cost a child-count pass and extra copies: only when the caller asked for one of them
@@ -2212,15 +2157,8 @@ int cc_engine_gather_cluster_points(cc_engine* e, int stream, int64_t n, const u
         return CC_ERR_INVALID_ARGUMENT;
     // one device block: descriptors (cid, n_points: u32; from, to, offset: i64), mismatch counter, outputs
     const size_t desc = (size_t) n * (4 + 4 + 8 + 8 + 8) + 64, outb = (size_t) total * (8 + 4) + 64;
-    // grow-only scratch owned by the engine (a hipMalloc / hipFree pair per call costs more than the gather)
-    if (e->gather_bytes < desc + outb)
-    {
-        void* p = nullptr;
-        CC_HIP_CHECK(e, hipMalloc(&p, (desc + outb) * 2));
-        e->allocations.push_back(p);
-        e->d_gather = (char*) p;
-        e->gather_bytes = (desc + outb) * 2;
-    }
+    if ((rc = ensure_gather(e, desc + outb)))
+        return rc;
     char* d = e->d_gather;
     auto fail = [&](int code) { return code; };
     cck::ClusterQuery q;
@@ -2292,184 +2230,13 @@ int cc_engine_set_option(cc_engine* e, const char* name, int64_t value)
     rc = finish_batch(e);
     if (rc)
         return rc;
-    const std::string n(name);
-    if (n == "resident")
-        e->resident_opt = value != 0;
-    else if (n == "mirror_views")
-        e->mirror_views = value != 0;
-    else if (n == "resident_idle_ms")
-        e->res_idle_ms = (int) std::max<int64_t>(1, std::min<int64_t>(value, 10000));
-    else if (n == "lds_tree_limit")
-        e->g.lds_tree_limit = (int32_t) (value < 1 ? 1 : (value > TREE_SLOTS ? TREE_SLOTS : value));
-    else if (n == "pipeline")
+    const OptionDef* d = cc_option_find(name);
+    if (!d)
     {
-        e->allow_pipeline = value != 0; // 0: one stream, 1: three chains, 2: four (window scan on its own stream)
-        e->pipeline_depth = value >= 2 ? 2 : 1;
-    }
-    else if (n == "graphs")
-        e->allow_graphs = value != 0;
-    else if (n == "sub_batch")
-        e->sub_batch = value < 0 ? 0 : value;
-    else if (n == "assoc_sweep_blocks")
-        e->assoc_sweep_blocks = value < 1 ? 1 : (value > 1024 ? 1024 : (int) value);
-    else if (n == "forget_inclination_table")
-    {
-        // sc_inclination_angles_between_lasers_ as a freshly constructed object has it (cc_engine_reset keeps it, like the reference's resize does):
-        // for callers that ran made-up data through a new engine (the drop-in class's warm-up)
-        if (value != 0)
-            CC_HIP_CHECK(e, hipMemset(e->P.curtab, 0xFF, (size_t) e->g.num_streams * (size_t) e->g.num_rows * sizeof(float)));
-    }
-    else if (n == "prewarm_small_graphs")
-    {
-        // Capturing and instantiating the graph of a call size takes milliseconds, once per size: a front-end that feeds a live sensor pays them
-        // here (the drop-in class does, in reset()), not in front of the first call of every size — with the asynchronous mode handing the engine
-        // whatever has queued up (1 .. 8 firings), eight such stalls of up to 30 ms each sat inside the first seconds of a stream
-        if (value != 0 && e->g.num_streams == 1)
-        {
-            // buffers first, sized for the largest call the drop-in class makes (a rotation of firings, when its caller ran ahead): growing them
-            // later re-allocates what the captured graphs point at, i.e. drops the graphs again
-            const size_t cap = (size_t) std::max(4096, e->g.num_columns);
-            if (e->ego_capacity < cap)
-            {
-                bool ok = true;
-                for (int i = 0; i < 4 && ok; i++)
-                    ok = alloc_plane(e, &e->d_ego[i], cap * cck::EGO_STRIDE) == CC_OK;
-                if (ok)
-                {
-                    e->ego_capacity = cap;
-                    e->small_graphs_stale = true;
-                }
-            }
-            (void) ensure_prep(e, (size_t) e->g.num_columns * (size_t) e->g.num_rows);
-            // the grow-only scratch of cc_engine_read_columns (a mirror reads a few columns per call; a device and a pinned host block) and of
-            // cc_engine_gather_cluster_points: a pinned allocation in front of the first finished cluster is a stall of milliseconds
-            {
-                const size_t vb = (size_t) 512 * e->g.num_rows * (5 * 4 + 8 + 3 * 8 + 3 + 8 + 4 + 8 + 8 + 5 * 4 + 1) + 256;
-                void* pv = nullptr;
-                if (e->view_bytes < vb && hipMalloc(&pv, vb) == hipSuccess)
-                {
-                    e->allocations.push_back(pv);
-                    e->d_view = pv;
-                    e->view_bytes = vb;
-                }
-                if (e->h_view_bytes < vb)
-                {
-                    if (e->h_view)
-                        (void) hipHostFree(e->h_view);
-                    e->h_view = nullptr;
-                    e->h_view_bytes = 0;
-                    if (hipHostMalloc((void**) &e->h_view, vb) == hipSuccess)
-                        e->h_view_bytes = vb;
-                }
-                const size_t gb = (size_t) 4 << 20;
-                void* pg = nullptr;
-                if (e->gather_bytes < gb && hipMalloc(&pg, gb) == hipSuccess)
-                {
-                    e->allocations.push_back(pg);
-                    e->d_gather = (char*) pg;
-                    e->gather_bytes = gb;
-                }
-            }
-            for (int64_t k = 1; k <= SMALL_MAX; k++)
-                (void) add_firings_small(e, 0, k, nullptr, nullptr, nullptr);
-        }
-    }
-    else if (n == "defer_tail_max_streams")
-        e->defer_tail_max_streams = value < 0 ? 0 : (int) value;
-    else if (n == "assoc_cooldown")
-        e->bail_cooldown_batches = value < 0 ? 0 : (value > 1000 ? 1000 : (int) value);
-    else if (n == "timing_every")
-        e->timing_every = value < 1 ? 1 : (int) value;
-    else if (n == "parallel_insert")
-    {
-        e->parallel_insert = value != 0;
-        e->parallel_insert_multi = value == 1;
-    }
-    else if (n == "input_on_engine_stream")
-        e->input_on_engine_stream = value != 0;
-    else if (n == "assoc_waves")
-    {
-        // 1: k_assoc_lds, 3: k_assoc3 without the links wave, 4: with it, 0 (default): k_assoc3, links wave up to 256 streams (2: as 3)
-        e->assoc_waves_auto = value <= 0 || value > 4;
-        e->assoc_waves = e->assoc_waves_auto ? 3 : (int) value;
-    }
-    else if (n == "insert_split_blocks")
-        e->insert_split_blocks = (int) (value < 0 ? 0 : (value > 8 ? 8 : value));
-    else if (n == "insert_wide_max_streams")
-        e->insert_wide_max_streams = value < 0 ? 0 : (value > (1 << 20) ? (1 << 20) : (int) value);
-    else if (n == "skip_idle_fallbacks")
-        e->skip_idle_fallbacks = value != 0;
-    else if (n == "fuse_front")
-        e->fuse_front = value != 0;
-    else if (n == "small_front")
-    {
-        e->small_front = value != 0;
-        e->small_graphs_stale = true;
-    }
-    else if (n == "small_all")
-    {
-        e->small_all = value != 0;
-        e->small_graphs_stale = true;
-    }
-    else if (n == "small_direct")
-        e->small_direct = value != 0;
-    else if (n == "check_input_lifetime")
-    {
-        int rcf = finish_batch(e);
-        if (rcf)
-            return rcf;
-        e->check_input_lifetime = (int) std::max<int64_t>(0, std::min<int64_t>(value, 2));
-        e->live_inputs.clear();
-    }
-    else if (n == "lazy_gate")
-    {
-        int rcf = flush_deferred(e);
-        if (rcf)
-            return rcf;
-        e->lazy_gate_max_streams = (int) std::max<int64_t>(0, std::min<int64_t>(value, 4096));
-        e->lazy_ok = true;
-        e->lazy_miss = 0;
-    }
-    else if (n == "lazy_gate_from")
-    {
-        int rcf = flush_deferred(e);
-        if (rcf)
-            return rcf;
-        e->lazy_gate_from_streams = (int) std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
-        e->lazy_ok = true;
-        e->lazy_miss = 0;
-    }
-    else if (n == "seg_small_max")
-    {
-        e->seg_small_max = value < 0 ? 0 : (value > 63 ? 63 : (int) value);
-        e->small_graphs_stale = true;
-    }
-    else if (n == "assoc_batch")
-        e->assoc_batch = value != 0;
-    else if (n == "assoc_rounds")
-        e->assoc_rounds = (int) (value < 0 ? 0 : (value > 8 ? 8 : value));
-    else if (n == "scan_store_fin")
-        e->scan_store_fin = value < 0 ? -1 : (value ? 1 : 0);
-    else if (n == "scan_split")
-        e->scan_split = (int) std::max<int64_t>(0, std::min<int64_t>(value, 2));
-    else if (n == "scan_cap")
-        e->g.scan_cap = (int) std::max<int64_t>(1, std::min<int64_t>(value, 1 << 20));
-    else if (n == "scan_long_records")
-        e->g.sl_cap = (int) std::max<int64_t>(1, std::min<int64_t>(value, cck::SL_CAP));
-    else if (n == "scan_packed")
-    {
-        e->scan_packed = value < 0 ? -1 : (value != 0 ? 1 : 0);
-    }
-    else if (n == "mirror_fields")
-        e->g.mirror_fields = value != 0;
-    else if (n == "limit_columns")
-        e->g.limit_columns = (int32_t) (value < 1 ? 1 : value);
-    else
-    {
-        e->error = "unknown option " + n;
+        e->error = std::string("unknown option ") + name;
         return CC_ERR_INVALID_ARGUMENT;
     }
-    return CC_OK;
+    return d->apply(e, cc_option_clamp(*d, value));
 }
 
 int cc_engine_enable_timing(cc_engine* e, int enable)
@@ -2563,15 +2330,8 @@ int cc_engine_scatter_info(cc_engine* e, int n, const int32_t* streams, const in
     }
     if (total == 0)
         return CC_OK;
-    const size_t need = total * 8 + 64;
-    if (e->gather_bytes < need)
-    {
-        void* p = nullptr;
-        CC_HIP_CHECK(e, hipMalloc(&p, need * 2));
-        e->allocations.push_back(p);
-        e->d_gather = (char*) p;
-        e->gather_bytes = need * 2;
-    }
+    if ((rc = ensure_gather(e, total * 8 + 64)))
+        return rc;
     int* d_min = (int*) e->d_gather;
     int* d_max = d_min + total;
     size_t o = 0;

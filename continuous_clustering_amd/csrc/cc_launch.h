@@ -1,6 +1,7 @@
 // cc_launch.h — the batch launch path of the engine: what goes onto which HIP stream, stage by stage, and launch_batch, which orders the stages of
 // one pass. Host code only. Not a header of its own: cc_engine.hip includes it once, inside its anonymous namespace, behind the definitions the
-// stages use (cc_engine, CC_HIP_CHECK, TimingMark, launch_prep, flush_deferred, the lazy-gate predicates, k_begin_batch, k_gate_out, finish_batch).
+// stages use (cc_engine, CC_HIP_CHECK, cc_buffers.h for ensure_ego, TimingMark, launch_prep, flush_deferred, the lazy-gate predicates, k_begin_batch,
+// k_gate_out, finish_batch).
 // ---- rows per lane -------------------------------------------------------------------------------------------------------------------------
 // The kernels that walk a column's rows are templates on the rows one lane holds (1: up to 64 rows, 2: up to 128). Every launch of one has ONE
 // argument list: CC_LAUNCH_RPL picks the instantiation from `rpl_`; CC_LAUNCH_RPL_MIRROR picks the <RPL, MIRROR> pair of the window scans
@@ -598,23 +599,6 @@ static int settle_lazy_batch(cc_engine* e, const BatchPass& bp, const std::funct
         rc = (*redo)();
     }
     return rc;
-}
-
-static int ensure_ego(cc_engine* e, size_t need)
-{
-    if (e->ego_capacity >= need)
-        return CC_OK;
-    // (old blocks stay in `allocations`; captured small-call graphs hold the old pointers and are dropped)
-    const size_t cap = need < 4096 ? 4096 : need;
-    for (int i = 0; i < 4; i++)
-    {
-        int rce = alloc_plane(e, &e->d_ego[i], cap * cck::EGO_STRIDE);
-        if (rce)
-            return rce;
-    }
-    e->ego_capacity = cap;
-    e->small_graphs_stale = true;
-    return CC_OK;
 }
 
 // One pass over a batch: insertion on `si`, table + segmentation on `sb`, window scan on `sc`, association + publish on `sa`
