@@ -18,7 +18,8 @@ import numpy as np
 from . import capi
 from .capi import Config
 
-__all__ = ["Config", "Engine", "EngineError", "load_library", "capi", "IDENTITY_TF"]
+__all__ = ["Config", "Engine", "EngineError", "load_library", "capi", "IDENTITY_TF", "take", "TAKE_POINT_DTYPE", "TAKE_STREAM_DTYPE",
+           "TakeCapacityError", "pointcloud2_fields"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.environ.get("CC_HIP_LIB", "libcc_hip.so"))  # (CC_HIP_LIB: another build of the same library, for A/B tools)
@@ -301,3 +302,13 @@ class Engine:
         g, i = C.c_void_p(), C.c_void_p()
         self._check(self.L.cc_engine_output_planes(self.h, stream, C.byref(g), C.byref(i)))
         return g.value, i.value
+
+
+# ---- hand-over of the published points in device memory (take.py) ---------------------------------------------------
+from . import take  # noqa: E402  (needs EngineError, _ptr and load_library from above)
+from .take import TAKE_POINT_DTYPE, TAKE_STREAM_DTYPE, TakeCapacityError, pointcloud2_fields  # noqa: E402
+
+Engine.take_points = take.take_points
+Engine.take_size = take.take_size
+Engine.take_cursor = take.take_cursor
+Engine.take_seek = take.take_seek

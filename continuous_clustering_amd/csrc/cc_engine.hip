@@ -193,6 +193,13 @@ struct cc_engine
     std::vector<char> state_cached;
     char* d_gather{nullptr}; // scratch of cc_engine_gather_cluster_points
     size_t gather_bytes{0};
+    // ---- cc_engine_take_points (cc_k_take.h): allocated by the first take, the device blocks again after a change of shape ----
+    long long* d_take_cursor{nullptr};     // [2 stages][streams] first column the next take hands over; 0 after create and after cc_engine_reset
+    cc_take_stream* d_take_plan{nullptr};  // [streams] the table of the take in flight
+    cck::TakeCtl* d_take_ctl{nullptr};
+    unsigned* d_take_counts{nullptr};      // [streams][take_stride] selected cells per column, then (scanned in place) the columns' first records
+    size_t take_counts_cap{0};
+    char* h_take{nullptr};                 // pinned: cc_take_stream[streams] | TakeCtl
     char* h_view{nullptr}; // pinned mirror of d_view: one D2H copy per read, the fields are split on the host
     size_t h_view_bytes{0};
     std::vector<std::vector<cc_event>> pending_events; // per stream, drained from the device after each batch
@@ -309,6 +316,11 @@ int free_all(cc_engine* e)
     e->ego_capacity = 0;
     e->d_gather = nullptr;
     e->gather_bytes = 0;
+    e->d_take_cursor = nullptr;
+    e->d_take_plan = nullptr;
+    e->d_take_ctl = nullptr;
+    e->d_take_counts = nullptr;
+    e->take_counts_cap = 0;
     e->d_small = nullptr;
     e->d_small_seq = nullptr; // (freed with the allocations above; the pinned counter below goes with it)
     e->d_input_sum = nullptr;
@@ -426,6 +438,8 @@ int reset_state(cc_engine* e, bool keep_table)
         st.assoc_mode = e->cfg.max_steps_in_row > WIN_COLS - 2 ? 1 : 0;
     }
     CC_HIP_CHECK(e, hipMemcpyAsync(e->d_states, init.data(), S * sizeof(StreamState), hipMemcpyHostToDevice, e->stream));
+    if (e->d_take_cursor) // (cc_engine_take_points: the hand-over starts again with the streams)
+        CC_HIP_CHECK(e, hipMemsetAsync(e->d_take_cursor, 0, 2 * S * sizeof(long long), e->stream));
     CC_HIP_CHECK(e, hipStreamSynchronize(e->stream));
     for (auto& v : e->pending_events)
         v.clear();
@@ -2204,6 +2218,150 @@ int cc_engine_gather_cluster_points(cc_engine* e, int stream, int64_t n, const u
         e->error = "cc_engine_gather_cluster_points: " + std::to_string(mismatch) + " cluster descriptor(s) do not match the engine state";
         return CC_ERR_INVALID_ARGUMENT;
     }
+    return CC_OK;
+}
+
+// ---- hand-over of the published points in device memory (cc_k_take.h) ----------------------------------------------
+// the cursors, the plan and the control block, by the first take (the device blocks again after a change of shape: free_all)
+static int ensure_take(cc_engine* e)
+{
+    const size_t S = (size_t) e->g.num_streams;
+    int rc;
+    if (!e->h_take && (rc = alloc_pinned(e, &e->h_take, S * sizeof(cc_take_stream) + sizeof(cck::TakeCtl), PIN_ENGINE)))
+        return rc;
+    if (e->d_take_cursor)
+        return CC_OK;
+    // (the members are set once all three blocks are there: a call that fails half way leaves nothing behind that a later call would take for complete)
+    long long* cur = nullptr;
+    cc_take_stream* plan = nullptr;
+    cck::TakeCtl* ctl = nullptr;
+    if ((rc = alloc_plane(e, &cur, 2 * S)) || (rc = alloc_plane(e, &plan, S)) || (rc = alloc_plane(e, &ctl, 1)))
+        return rc;
+    // (in stream order and waited for: a hipMemset on the null stream is not ordered against the engine's streams, and recycled device memory is not zero)
+    CC_HIP_CHECK(e, hipMemsetAsync(cur, 0, 2 * S * sizeof(long long), query_stream(e)));
+    CC_HIP_CHECK(e, hipStreamSynchronize(query_stream(e)));
+    e->d_take_plan = plan;
+    e->d_take_ctl = ctl;
+    e->d_take_cursor = cur;
+    return CC_OK;
+}
+
+// what the three take functions share: arguments, the resident kernel, the batches in flight, the buffers
+static int take_enter(cc_engine* e, const char* who, int stage)
+{
+    if (!e)
+        return CC_ERR_INVALID_ARGUMENT;
+    if (stage != CC_TAKE_CLUSTERED && stage != CC_TAKE_SEGMENTED)
+    {
+        e->error = std::string(who) + ": stage must be CC_TAKE_CLUSTERED or CC_TAKE_SEGMENTED";
+        return CC_ERR_INVALID_ARGUMENT;
+    }
+    if (e->resident_opt)
+    {
+        e->error = std::string(who) + ": not available while the option \"resident\" is on (the resident kernel owns the stream's state); set it to 0 first";
+        return CC_ERR_INVALID_ARGUMENT;
+    }
+    (void) hipSetDevice(e->device);
+    int rc = finish_batch(e);
+    if (rc)
+        return rc;
+    return ensure_take(e);
+}
+
+int cc_engine_take_points(cc_engine* e, int stage, int select, cc_take_point* d_records, int64_t capacity, cc_take_stream* d_table,
+                          cc_take_stream* h_table, int64_t* n_records)
+{
+    if (!e)
+        return CC_ERR_INVALID_ARGUMENT;
+    const char* bad = nullptr;
+    if (select != CC_TAKE_ALL_RETURNS && select != CC_TAKE_NOT_GROUND && select != CC_TAKE_WITH_ID)
+        bad = "select must be CC_TAKE_ALL_RETURNS, CC_TAKE_NOT_GROUND or CC_TAKE_WITH_ID";
+    else if (select == CC_TAKE_WITH_ID && stage == CC_TAKE_SEGMENTED)
+        bad = "CC_TAKE_WITH_ID needs the CLUSTERED stage (segmented columns have no final ids)";
+    else if (capacity < 0 || (!d_records && capacity != 0))
+        bad = "capacity must be >= 0, and 0 without a record array (the size query)";
+    else if (((uintptr_t) d_records & 15u) != 0)
+        bad = "d_records must be 16-byte aligned";
+    else if (!h_table || !n_records)
+        bad = "h_table and n_records must not be NULL";
+    if (bad)
+    {
+        e->error = std::string("cc_engine_take_points: ") + bad;
+        return CC_ERR_INVALID_ARGUMENT;
+    }
+    int rc = take_enter(e, "cc_engine_take_points", stage);
+    if (rc)
+        return rc;
+    const int S = e->g.num_streams;
+    hipStream_t q = query_stream(e);
+    cc_take_stream* h_plan = (cc_take_stream*) e->h_take;
+    cck::TakeCtl* h_ctl = (cck::TakeCtl*) (e->h_take + (size_t) S * sizeof(cc_take_stream));
+    hipLaunchKernelGGL(cck::k_take_plan, dim3((unsigned) ((S + 63) / 64)), dim3(64), 0, q, e->g, e->d_states, e->d_take_cursor, stage, e->d_take_plan, h_plan);
+    CC_HIP_CHECK(e, hipGetLastError());
+    CC_HIP_CHECK(e, hipStreamSynchronize(q));
+    // the grids follow the longest range of the plan, not the ring
+    int64_t longest = 0;
+    for (int s = 0; s < S; s++)
+        longest = std::max<int64_t>(longest, h_plan[s].col_to - h_plan[s].col_from);
+    if (longest > e->g.ring_cols)
+    {
+        e->error = "cc_engine_take_points: a range longer than the ring";
+        return CC_ERR_BOOKKEEPING;
+    }
+    const int stride = (int) std::max<int64_t>(longest, 1);
+    // (twice what is needed, at most a ring per stream: ranges that creep up from take to take must not allocate a new block each time)
+    const size_t counts_need = (size_t) S * (size_t) stride;
+    if ((rc = grow_scratch(e, &e->d_take_counts, &e->take_counts_cap, counts_need, std::min(2 * counts_need, (size_t) S * (size_t) e->g.ring_cols))))
+        return rc;
+    if (longest > 0)
+        hipLaunchKernelGGL(cck::k_take_count, dim3((unsigned) longest, (unsigned) S), dim3(64), 0, q, e->g, e->P, e->d_take_plan, select, e->d_take_counts, stride);
+    hipLaunchKernelGGL(cck::k_take_scan, dim3((unsigned) S), dim3(cck::TAKE_SCAN_THREADS), 0, q, e->d_take_plan, e->d_take_counts, stride);
+    hipLaunchKernelGGL(cck::k_take_scan_streams, dim3(1), dim3(cck::TAKE_SCAN_THREADS), 0, q, S, e->d_take_plan, (long long) capacity, d_records ? 1 : 0,
+                       e->d_take_ctl, d_table, h_plan, h_ctl);
+    if (d_records) // (the kernel looks at the verdict itself: nothing is written and no cursor moves unless every record fits)
+        hipLaunchKernelGGL(cck::k_take_write, dim3((unsigned) stride, (unsigned) S), dim3(64), 0, q, e->g, e->P, e->d_take_plan, e->d_take_ctl, stage, select,
+                           e->d_take_counts, stride, d_records, e->d_take_cursor);
+    CC_HIP_CHECK(e, hipGetLastError());
+    CC_HIP_CHECK(e, hipStreamSynchronize(q));
+    memcpy(h_table, h_plan, (size_t) S * sizeof(cc_take_stream));
+    *n_records = h_ctl->total;
+    if (h_ctl->total > capacity)
+    {
+        e->error = "cc_engine_take_points: " + std::to_string(h_ctl->total) + " records do not fit a capacity of " + std::to_string(capacity) +
+                   " (nothing was written, no cursor moved)";
+        return CC_ERR_CAPACITY;
+    }
+    return CC_OK;
+}
+
+int cc_engine_take_cursor(cc_engine* e, int stage, int stream, int64_t* cursor, int64_t* readable_from)
+{
+    if (!e || stream < 0 || stream >= e->g.num_streams)
+        return CC_ERR_INVALID_ARGUMENT;
+    int rc = take_enter(e, "cc_engine_take_cursor", stage);
+    if (rc)
+        return rc;
+    long long cur = 0;
+    StreamState st;
+    CC_HIP_CHECK(e, hipMemcpy(&cur, e->d_take_cursor + (size_t) stage * e->g.num_streams + stream, sizeof(cur), hipMemcpyDeviceToHost));
+    CC_HIP_CHECK(e, hipMemcpy(&st, e->d_states + stream, sizeof(st), hipMemcpyDeviceToHost));
+    if (cursor)
+        *cursor = cur;
+    if (readable_from)
+        *readable_from = std::max<int64_t>(0, std::max(st.clear_done, st.first_column));
+    return CC_OK;
+}
+
+int cc_engine_take_seek(cc_engine* e, int stage, int stream, int64_t column)
+{
+    if (!e || stream < -1 || stream >= e->g.num_streams || column < 0)
+        return CC_ERR_INVALID_ARGUMENT;
+    int rc = take_enter(e, "cc_engine_take_seek", stage);
+    if (rc)
+        return rc;
+    const int first = stream < 0 ? 0 : stream, count = stream < 0 ? e->g.num_streams : 1;
+    const std::vector<long long> v((size_t) count, (long long) column);
+    CC_HIP_CHECK(e, hipMemcpy(e->d_take_cursor + (size_t) stage * e->g.num_streams + first, v.data(), (size_t) count * sizeof(long long), hipMemcpyHostToDevice));
     return CC_OK;
 }
 

@@ -17,6 +17,7 @@
 //   cc_assoc_shared.h, cc_assoc3.h   k_assoc3: three / four cooperating wavefronts per stream, the exact serial kernel behind k_assocb
 //   cc_assocb.h          k_assocb: batch-parallel association + finished-cluster check (groups of columns, pipelined, points packed into lanes)
 //   cc_k_publish.h       k_publish, k_small_tail, frame scatter, cluster gathering, host view
+//   cc_k_take.h          k_take_plan / count / scan / write: the published points of all streams, compacted in device memory
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,5 +41,6 @@ using namespace ccd;
 #include "cc_assoc3.h"
 #include "cc_assocb.h"
 #include "cc_k_publish.h"
+#include "cc_k_take.h"
 
 } // namespace cck

@@ -288,6 +288,50 @@ int cc_engine_output_planes(cc_engine* e, int stream, const uint8_t** d_ground_l
 int cc_engine_gather_cluster_points(cc_engine* e, int stream, int64_t n, const uint32_t* cluster_ids, const int64_t* col_from,
                                     const int64_t* col_to, const uint32_t* n_points, int64_t* h_gcol, int32_t* h_row);
 
+/* ---- device-to-device hand-over of what was published since the last hand-over, all streams at once ----
+ * The engine keeps one cursor per (stage, stream) in device memory, 0 after create and after cc_engine_reset. A take hands over the columns
+ * [max(cursor, columns cleared already, first column of the stream), upper) of every stream, upper = first_unpublished (CLUSTERED) or
+ * first_unfinished (SEGMENTED), as compacted records in DEVICE memory, ordered by stream, then global column, then row, and moves the
+ * cursors to `upper`. A stream that has not started hands over an empty range. A cell is a return under the rule of
+ * cc_engine_read_columns (distance is not NaN and the cell was filled in this pass over the ring). */
+enum { CC_TAKE_CLUSTERED = 0,   /* columns below first_unpublished: ids final            */
+       CC_TAKE_SEGMENTED = 1 }; /* columns below first_unfinished: ground labels final, id written as 0 */
+enum { CC_TAKE_ALL_RETURNS = 0, /* every cell that holds a return                         */
+       CC_TAKE_NOT_GROUND  = 1, /* ... whose ground_point_label != CC_GP_GROUND           */
+       CC_TAKE_WITH_ID     = 2 };/* ... whose cluster id != 0 (CLUSTERED stage only)      */
+
+typedef struct cc_take_point {   /* 32 bytes (the record ARRAY, d_records, must be 16-byte aligned): also a valid PointCloud2 point (point_step 32) */
+    float x, y, z;               /* odom frame (Point::xyz)                                */
+    float distance;
+    uint32_t id;                 /* cluster id, reference numbering; 0 in the SEGMENTED stage */
+    uint32_t source_firing;      /* low 32 bits of cc_column_view::source_firing           */
+    uint16_t row;
+    uint8_t  ground_point_label;
+    uint8_t  intensity;
+    uint32_t column;             /* global column - cc_take_stream::col_from of its stream */
+} cc_take_point;
+
+typedef struct cc_take_stream {  /* one per stream, 48 bytes */
+    int64_t col_from, col_to;    /* columns [col_from, col_to) were handed over (col_to == col_from: nothing new) */
+    int64_t lost_columns;        /* columns between the cursor and col_from that had been cleared already */
+    int64_t first_record, n_records; /* this stream's slice of the record array            */
+    int32_t error;               /* the stream's CC_ERR_* (then n_records == 0 and the cursor stays) */
+    int32_t pad;
+} cc_take_stream;
+
+/* Take. d_records: device, `capacity` records, 16-byte aligned; d_table (device, may be NULL) and h_table (host) receive num_streams entries;
+ * *n_records = records of all streams. If they exceed `capacity`: CC_ERR_CAPACITY, *n_records and h_table say what is needed, nothing is
+ * written to d_records and no cursor moves (all or nothing) - a retry with a larger buffer returns what a first call would have.
+ * d_records == NULL with capacity == 0 is the size query: it never moves a cursor (CC_OK when there is nothing to take). Finishes the
+ * submitted batches first and returns with the records complete. Refused (CC_ERR_INVALID_ARGUMENT) while the option "resident" is on. */
+int cc_engine_take_points(cc_engine* e, int stage, int select, cc_take_point* d_records, int64_t capacity,
+                          cc_take_stream* d_table /* may be NULL */, cc_take_stream* h_table /* [num_streams] */,
+                          int64_t* n_records);
+/* The cursor of (stage, stream) and the lowest column a take could still hand over (what has been cleared lies below it); either may be NULL. */
+int cc_engine_take_cursor(cc_engine* e, int stage, int stream, int64_t* cursor, int64_t* readable_from);
+/* Set the cursor of (stage, stream), stream = -1: of every stream, to `column` (>= 0): skip ahead, or hand columns over again. */
+int cc_engine_take_seek(cc_engine* e, int stage, int stream /* -1: all */, int64_t column);
+
 /* Engine tuning / test hooks: one option per line, `name` (default) meaning. Values out of range are clamped. Environment variables that override
  * options (CC_ASSOC_ROUNDS, CC_DEFER_TAIL, ... as used by the A/B tools) are only read when CC_ENABLE_ENV_OPTS=1 is set. Every setting gives the
  * same results (the parity tests run over them, tests/test_gpu_stress.py walks random combinations); they only move work between kernels and streams.
