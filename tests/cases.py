@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import numpy as np
 
+import profile_streams
 from continuous_clustering_amd import capi, synth
 from continuous_clustering_amd.synth import Motion, SceneModel, SensorModel
 
@@ -55,7 +56,137 @@ ROBOT_TF_TILTED = np.array([0.9961946980917455, 0.0, 0.08715574274765817, 1.2,
                             -0.08715574274765817, 0.0, 0.9961946980917455, 0.3], dtype=np.float64)
 
 
+# ---- slope-controlled columns (profile_streams.py): name -> (rows, columns, top / bottom inclination in degrees, config, seed).
+# 2 rotations + a quarter: a full rotation, the ring start and several 64-column tiles with a partial last one.
+PROFILE_SENSORS = {
+    "p_s64_profiles": (64, 360, 2.0, -24.8, _kitti, 301),
+    "p_s128_profiles": (128, 340, 15.0, -25.0, _vls, 302),
+    "p_s40_profiles": (40, 360, 7.0, -18.0, _kitti, 303),   # rows: a multiple of 8, not of 16
+    "p_s50_profiles": (50, 360, 3.0, -25.0, _kitti, 304),   # rows: no multiple of 8
+    "p_s16_profiles": (16, 360, 1.0, -29.0, _kitti, 305),
+}
+
+
+def profile_sensor(name):
+    rows, cols, top, bottom, _, _ = PROFILE_SENSORS[name]
+    return SensorModel(num_rows=rows, num_columns=cols, incl_top_deg=top, incl_bottom_deg=bottom)
+
+
+def profile_stream(name, seed=None, moving=False):
+    """The stream of a p_* case; with another seed: another stream of the same sensor (multi-stream tests); moving: the same returns under a
+    pose sequence that drives, yaws, rolls and pitches (the ego-box cases)."""
+    rows, cols, _, _, _, seed0 = PROFILE_SENSORS[name]
+    n = 2 * cols + cols // 4
+    poses = profile_streams.moving_poses(n, 900 + seed0) if moving else None
+    return profile_streams.make_profile_stream(profile_sensor(name), n, seed0 if seed is None else seed, poses=poses)
+
+
+def profile_config(name, **over):
+    return PROFILE_SENSORS[name][4](PROFILE_SENSORS[name][1], **over)
+
+
+# One field or pair per entry, against the base configuration of the case. tests/test_profile_cases_cpu.py shows on the oracle that every entry
+# changes at least 100 cells (or the events) of p_s64_profiles; tests/test_gpu_segmentation_sweep.py runs the engine under each of them.
+FOG = dict(fog_filtering_enabled=1, fog_filtering_intensity_below=128, fog_filtering_distance_below=12.0, fog_filtering_inclination_above=-0.25)
+SEGMENTATION_SWEEP = {
+    "use_terrain": dict(use_terrain=1),
+    "max_slope_0.05": dict(max_slope=0.05),
+    "max_slope_0.21": dict(max_slope=0.21),
+    "max_slope_1.0": dict(max_slope=1.0),
+    "first_ring_max_0.1": dict(first_ring_as_ground_max_allowed_z_diff=0.1),
+    "first_ring_min_-0.1": dict(first_ring_as_ground_min_allowed_z_diff=-0.1),
+    "last_ground_slope_0.1": dict(last_ground_point_slope_higher_than=0.1),
+    "last_ground_slope_-10": dict(last_ground_point_slope_higher_than=-10.0),
+    "last_ground_distance_0.5": dict(last_ground_point_distance_smaller_than=0.5),
+    "close_to_ground_z_0.05": dict(ground_because_close_to_last_certain_ground_max_z_diff=0.05),
+    "close_to_ground_dist_0.3": dict(ground_because_close_to_last_certain_ground_max_dist_diff=0.3),
+    "next_obstacle_dist_0": dict(obstacle_because_next_certain_obstacle_max_dist_diff=0.0),
+    "next_obstacle_dist_3.0": dict(obstacle_because_next_certain_obstacle_max_dist_diff=3.0),
+    "no_supplement": dict(supplement_inclination_angle_for_nan_cells=0),
+    "no_inclination_ignore": dict(ignore_points_with_too_big_inclination_angle_diff=0),
+    "chessboard": dict(ignore_points_in_chessboard_pattern=1),
+    "max_distance_0.05": dict(max_distance=0.05),
+    "max_distance_3.0": dict(max_distance=3.0),
+    "fog": FOG,
+}
+ASSOCIATION_SWEEP = {
+    "max_steps_in_column_1": dict(max_steps_in_column=1),
+    "max_steps_in_column_3": dict(max_steps_in_column=3),
+    "max_steps_in_row_1": dict(max_steps_in_row=1),
+    "max_steps_in_row_4": dict(max_steps_in_row=4),
+    "min_steps_5": dict(stop_after_association_min_steps=5),
+}
+# a value from each row of the two tables at once (use_terrain = 1 switches the YELLOW / YELLOWGREEN rules off, so the second entry keeps them)
+EVERYTHING = dict(use_terrain=1, max_slope=0.21, first_ring_as_ground_max_allowed_z_diff=0.1, first_ring_as_ground_min_allowed_z_diff=-0.1,
+                  last_ground_point_slope_higher_than=0.1, last_ground_point_distance_smaller_than=0.5,
+                  ground_because_close_to_last_certain_ground_max_z_diff=0.05, ground_because_close_to_last_certain_ground_max_dist_diff=0.3,
+                  obstacle_because_next_certain_obstacle_max_dist_diff=3.0, supplement_inclination_angle_for_nan_cells=0,
+                  ignore_points_with_too_big_inclination_angle_diff=0, ignore_points_in_chessboard_pattern=1, max_distance=3.0,
+                  max_steps_in_column=3, max_steps_in_row=4, stop_after_association_min_steps=5, **FOG)
+EVERYTHING_NO_TERRAIN = dict(EVERYTHING, use_terrain=0)
+SWEEP_BASE_CASE = "p_s64_profiles"
+
+
+def sweep_overrides(entry):
+    if entry == "base":
+        return {}
+    if entry == "everything":
+        return EVERYTHING
+    if entry == "everything_no_terrain":
+        return EVERYTHING_NO_TERRAIN
+    return SEGMENTATION_SWEEP[entry] if entry in SEGMENTATION_SWEEP else ASSOCIATION_SWEEP[entry]
+
+
+# ---- ego box: robot_from_sensor and box settings for p_s64_profiles under the moving pose sequence. (name -> (robot_from_sensor, overrides))
+ROBOT_TF_AHEAD_ABOVE = np.array([1.0, 0.0, 0.0, 6.0,
+                                 0.0, 1.0, 0.0, 0.0,
+                                 0.0, 0.0, 1.0, 2.0], dtype=np.float64)
+ROBOT_TF_1M_UP = np.array([1.0, 0.0, 0.0, 0.0,
+                           0.0, 1.0, 0.0, 0.0,
+                           0.0, 0.0, 1.0, 1.0], dtype=np.float64)
+EGO_SETTINGS = {
+    "tilted_tf": (ROBOT_TF_TILTED, {}),
+    "sensor_ahead_above": (ROBOT_TF_AHEAD_ABOVE, dict(height_ref_to_ground_=0.3, height_ref_to_maximum_=2.5, length_ref_to_front_end_=9.0)),
+    "asymmetric_box": (None, dict(length_ref_to_front_end_=12.0, length_ref_to_rear_end_=-0.5, width_ref_to_left_mirror_=0.3, width_ref_to_right_mirror_=-4.0)),
+    "box_without_sensor": (None, dict(length_ref_to_front_end_=9.0, length_ref_to_rear_end_=1.5, width_ref_to_left_mirror_=5.0, width_ref_to_right_mirror_=0.5)),
+    "empty_box": (None, dict(length_ref_to_front_end_=-1.0, length_ref_to_rear_end_=1.0)),
+    "huge_box": (None, dict(length_ref_to_front_end_=200.0, length_ref_to_rear_end_=-200.0, width_ref_to_left_mirror_=200.0,
+                            width_ref_to_right_mirror_=-200.0, height_ref_to_maximum_=200.0, height_ref_to_ground_=-200.0)),
+    # returns above the box exist only where the sensor sits low in it: mounted 1 m above the robot's origin the plain box ends 0.5 m below the
+    # sensor (walls next to the sensor rise above that), the box with height_ref_to_maximum_ = 5 takes them in
+    "sensor_1m_up": (ROBOT_TF_1M_UP, dict(height_ref_to_ground_=-0.7)),
+    "height_max_5": (ROBOT_TF_1M_UP, dict(height_ref_to_ground_=-0.7, height_ref_to_maximum_=5.0)),
+}
+
+
+def ego_case(setting):
+    tf, over = EGO_SETTINGS[setting]
+    return profile_stream(SWEEP_BASE_CASE, moving=True), profile_config(SWEEP_BASE_CASE, **over), tf
+
+
 def build_case(name: str):
+    if name in PROFILE_SENSORS:
+        return profile_stream(name), profile_config(name), None
+    if name == "p_s64_profiles_moving":
+        return profile_stream(SWEEP_BASE_CASE, moving=True), profile_config(SWEEP_BASE_CASE), None
+    if name == "p_s64_alternating":
+        # ground / obstacle changes on every second valid row: the input on which k_seg_small's fixed point over the labels needs many rounds.
+        # The risers are 3 - 10 cm apart from the treads below them, so the two distance rules that would merge them are tightened: an obstacle only
+        # pulls ground within 2 cm with it, and "close to the last certain ground" reaches 5 cm.
+        cfg = _kitti(360, obstacle_because_next_certain_obstacle_max_dist_diff=0.02, ground_because_close_to_last_certain_ground_max_dist_diff=0.05)
+        return profile_streams.make_alternating_stream(_s64(360), 120, 311), cfg, None
+    if name == "p_s64_terrain_gaps":
+        # use_terrain = 1 on smooth ground with many missing rows: the rule that a ground point more than 5 m beyond the previous one is an obstacle
+        # (cc.cpp: the terrain branch of "flat w.r.t. the previous point") decides the first obstacle of most columns
+        mix = profile_streams.Mixture(flat=0.55, edge=0.0, mild=0.05, steep=0.0, wall=0.0, step=0.0, missing=0.40, near_start=0.0,
+                                      first_weights=(0.3, 0.3, 0.0, 0.0, 0.2, 0.2))
+        return profile_streams.make_profile_stream(_s64(360), 810, 313, mix=mix), _kitti(360, use_terrain=1), None
+    if name == "p_s64_label_chains":
+        # one-row walls and flat rows in turn, thresholds from the sweep table: the labels form a dependency chain over the whole column, so that an
+        # iteration over the labels (k_seg_small) needs about rows / 2 rounds (tests/test_profile_cases_cpu.py counts them)
+        sen = SensorModel(num_rows=64, num_columns=360, incl_top_deg=-12.0, incl_bottom_deg=-30.0)
+        cfg = _kitti(360, max_slope=1.0, ground_because_close_to_last_certain_ground_max_z_diff=0.03)
+        return profile_streams.make_chain_stream(sen, 120, 312), cfg, None
     if name == "s64_static":
         return synth.make_stream(720 * 3, seed=1234, sensor=_s64(720)), _kitti(720), None
     if name == "s64_translate":
@@ -258,6 +389,9 @@ EXCEPTION_CASES = ["x_s64_slanted_gaps", "x_s64_slanted_gaps_far", "x_s64_near_j
 CLUTTER_CASES = ["c_s64_sparse_clutter", "c_s64_near_clutter", "c_s64_mixed_clutter", "c_s128_sparse_clutter"]
 
 RING_WRAP_CASES = ["w_s64_240x13", "w_s64_360x12_turn", "w_s64_ring_wall_240x12", "w_s128_offsets_340x12", "w_s32_256x12"]
+
+PROFILE_CASES = list(PROFILE_SENSORS)
+FIXED_POINT_CASES = ["p_s64_alternating", "p_s64_label_chains"]
 
 # cases stored as golden fixtures under tests/golden/ (inputs + expected outputs)
 GOLDEN_CASES = ["g_s64_translate", "g_s64_forced_finish_ring", "g_s128_offsets", "g_s64_fog_and_ego"]

@@ -259,12 +259,28 @@ class Independent:
 
 
 INDEPENDENT_CASES = ["g_s64_translate", "g_s64_fog_and_ego", "g_s128_offsets", "s64_turn", "s64_counterclockwise", "s64_dropouts",
-                     "s64_no_supplement_no_incl_ignore", "s32_small_sensor", "j_s64_jitter", "j_s64_jitter_wide", "j_s128_offsets_jitter", "s64_deep_lookback"]
+                     "s64_no_supplement_no_incl_ignore", "s32_small_sensor", "j_s64_jitter", "j_s64_jitter_wide", "j_s128_offsets_jitter", "s64_deep_lookback",
+                     "p_s64_profiles", "p_s40_profiles", "p_s128_profiles"]
+
+# the slope-controlled columns under the configurations whose branches no other case takes (tests/test_gpu_segmentation_sweep.py judges the kernels
+# by the oracle under exactly these)
+INDEPENDENT_SWEPT = ["use_terrain", "close_to_ground_z_0.05+close_to_ground_dist_0.3", "last_ground_slope_0.1"]
 
 
 @pytest.mark.parametrize("name", INDEPENDENT_CASES)
 def test_second_restatement_of_insertion_and_segmentation_agrees_with_the_oracle(name, oracle_lib):
-    stream, cfg, tf = cases.build_case(name)
+    check_against_the_oracle(*cases.build_case(name))
+
+
+@pytest.mark.parametrize("entries", INDEPENDENT_SWEPT)
+def test_second_restatement_agrees_with_the_oracle_under_swept_thresholds(entries, oracle_lib):
+    over = {}
+    for e in entries.split("+"):
+        over.update(cases.sweep_overrides(e))
+    check_against_the_oracle(cases.profile_stream(cases.SWEEP_BASE_CASE), cases.profile_config(cases.SWEEP_BASE_CASE, **over), None)
+
+
+def check_against_the_oracle(stream, cfg, tf):
     n = min(stream.n_firings, 1100)
     from oracle.pyoracle import Oracle, IDENTITY_TF
     robot = IDENTITY_TF if tf is None else tf

@@ -64,13 +64,19 @@ def compare_columns(ao: dict, ae: dict, c0: int, check_raw_ids=True, mirror=True
         assert bad.size == 0, f"raw cluster ids differ at (col {c0 + bad[0][0]}, row {bad[0][1]})"
 
 
-def run_and_compare(stream, cfg, chunks=None, robot_tf=None, expect_rc=0, check_raw_ids=True, engine_setup=None):
-    """Feed `stream` to the oracle (all at once) and to a 1-stream engine (in `chunks` firings per call); after every
-    engine call compare the events it produced and the columns it published with the oracle's record."""
-    from continuous_clustering_amd import Engine, IDENTITY_TF
+def oracle_record(stream, cfg, robot_tf=None):
+    """The oracle's side of run_and_compare, for tests that put several engine runs against one oracle run: (oracle, status, events)."""
     oracle, orc = run_oracle(stream, cfg, robot_tf)
+    return oracle, orc, oracle.drain_events()
+
+
+def run_and_compare(stream, cfg, chunks=None, robot_tf=None, expect_rc=0, check_raw_ids=True, engine_setup=None, oracle=None):
+    """Feed `stream` to the oracle (all at once) and to a 1-stream engine (in `chunks` firings per call); after every
+    engine call compare the events it produced and the columns it published with the oracle's record (`oracle`: the
+    oracle_record of this stream, configuration and transform from an earlier run)."""
+    from continuous_clustering_amd import Engine, IDENTITY_TF
+    oracle, orc, eo = oracle if oracle is not None else oracle_record(stream, cfg, robot_tf)
     assert orc == expect_rc, f"oracle rc {orc} ({oracle.last_error()}), expected {expect_rc}"
-    eo = oracle.drain_events()
     engine = Engine(cfg, stream.sensor.num_rows, 1, 0, IDENTITY_TF if robot_tf is None else robot_tf)
     if engine_setup is not None:
         engine_setup(engine)

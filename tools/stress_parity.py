@@ -1,5 +1,7 @@
 """Randomised parity sweep (GPU box): many small scenes with lots of short-lived trees, odd chunkings, both sensors, both
-association kernels. Engine vs oracle through tests/util.run_and_compare. Usage: python tools/stress_parity.py [n_cases] [seed0]"""
+association kernels. Engine vs oracle through tests/util.run_and_compare. Usage: python tools/stress_parity.py [--thresholds] [n_cases] [seed0]
+--thresholds: every case also takes three entries of the threshold sweep (tests/cases.py: SEGMENTATION_SWEEP, ASSOCIATION_SWEEP), drawn from a
+generator of their own, so that the scenes, chunkings and options of a seed are the same with and without the switch."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -10,8 +12,12 @@ from continuous_clustering_amd.synth import Motion, SceneModel
 from oracle import pyoracle
 pyoracle.build()
 
-n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 12
-seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
+args = [a for a in sys.argv[1:] if a != "--thresholds"]
+thresholds = "--thresholds" in sys.argv[1:]
+n_cases = int(args[0]) if len(args) > 0 else 12
+seed0 = int(args[1]) if len(args) > 1 else 1000
+# (read only with the switch: without it the tool needs nothing of tests/cases.py beyond the sensors and configurations it always used)
+SWEPT = {**cases.SEGMENTATION_SWEEP, **cases.ASSOCIATION_SWEEP} if thresholds else {}
 bad = 0
 for i in range(n_cases):
     rng = np.random.default_rng(seed0 + i)
@@ -30,6 +36,12 @@ for i in range(n_cases):
         over["max_distance"] = float(rng.choice([0.4, 0.7, 1.2]))
     if rng.random() < 0.2:
         over["stop_after_association_enabled"] = 0
+    swept = []
+    if thresholds:
+        trng = np.random.default_rng([seed0 + i, 7])
+        swept = [str(k) for k in trng.choice(sorted(SWEPT), size=3, replace=False)]
+        for k in swept:
+            over.update(SWEPT[k])
     cfg = (cases._vls if s128 else cases._kitti)(cols, **over)
     chunks = [int(c) for c in rng.choice([1, 3, 17, 64, 97, 250, cols, 2 * cols], size=4)]
     waves = [0, 4, 3, 1][i % 4]  # default (k_assoc3 + links wavefront), pinned four / three waves, k_assoc_lds
@@ -44,9 +56,9 @@ for i in range(n_cases):
         bc = box["e"].batch_counters()
         print(f"case {i:3d} ok: rows {sensor.num_rows} cols {cols} firings {n} objects {scene.n_objects} chunks {chunks} waves {waves} "
               f"clusters {summ['clusters']} serial columns {es['error_b']} batch {batch} rounds {rounds} columns {bc['batch_columns']} "
-              f"bails {bc['batch_bails']} {bc['bail_reasons'][1:7]}", flush=True)
+              f"bails {bc['batch_bails']} {bc['bail_reasons'][1:7]}" + (f" thresholds {swept}" if thresholds else ""), flush=True)
     except AssertionError as ex:
         bad += 1
-        print(f"case {i:3d} FAILED (seed {seed0 + i}): {str(ex)[:300]}", flush=True)
+        print(f"case {i:3d} FAILED (seed {seed0 + i}{', thresholds ' + str(swept) if thresholds else ''}): {str(ex)[:300]}", flush=True)
 print("failures:", bad)
 sys.exit(1 if bad else 0)
