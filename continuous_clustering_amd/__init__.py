@@ -19,7 +19,7 @@ from . import capi
 from .capi import Config
 
 __all__ = ["Config", "Engine", "EngineError", "load_library", "capi", "IDENTITY_TF", "take", "TAKE_POINT_DTYPE", "TAKE_STREAM_DTYPE",
-           "TakeCapacityError", "pointcloud2_fields"]
+           "TakeCapacityError", "pointcloud2_fields", "TAKE_CLUSTER_DTYPE", "TAKE_CLUSTER_STREAM_DTYPE"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.environ.get("CC_HIP_LIB", "libcc_hip.so"))  # (CC_HIP_LIB: another build of the same library, for A/B tools)
@@ -307,8 +307,12 @@ class Engine:
 # ---- hand-over of the published points in device memory (take.py) ---------------------------------------------------
 from . import take  # noqa: E402  (needs EngineError, _ptr and load_library from above)
 from .take import TAKE_POINT_DTYPE, TAKE_STREAM_DTYPE, TakeCapacityError, pointcloud2_fields  # noqa: E402
+from .take import TAKE_CLUSTER_DTYPE, TAKE_CLUSTER_STREAM_DTYPE  # noqa: E402
 
 Engine.take_points = take.take_points
 Engine.take_size = take.take_size
 Engine.take_cursor = take.take_cursor
 Engine.take_seek = take.take_seek
+Engine.take_clusters = take.take_clusters
+Engine.take_clusters_size = take.take_clusters_size
+Engine.take_clusters_cursor = take.take_clusters_cursor

@@ -200,6 +200,14 @@ struct cc_engine
     unsigned* d_take_counts{nullptr};      // [streams][take_stride] selected cells per column, then (scanned in place) the columns' first records
     size_t take_counts_cap{0};
     char* h_take{nullptr};                 // pinned: cc_take_stream[streams] | TakeCtl
+    // ---- cc_engine_take_clusters (cc_k_take_clusters.h): allocated by the first take, the device blocks again after a change of shape ----
+    long long* d_tc_cursor{nullptr};            // [streams][2] ids taken (next_id - 1), floor column; 0 after create and after cc_engine_reset
+    cck::TcPlan* d_tc_plan{nullptr};            // [streams]
+    cc_take_cluster_stream* d_tc_table{nullptr}; // [streams] the table of the take in flight
+    cck::TcCtl* d_tc_ctl{nullptr};
+    cck::TcSlot* d_tc_slots{nullptr};           // the aggregate table: one slot per examined id, all streams
+    size_t tc_slots_cap{0};
+    char* h_tc{nullptr};                        // pinned: TcPlan[streams] | cc_take_cluster_stream[streams] | TcCtl
     char* h_view{nullptr}; // pinned mirror of d_view: one D2H copy per read, the fields are split on the host
     size_t h_view_bytes{0};
     std::vector<std::vector<cc_event>> pending_events; // per stream, drained from the device after each batch
@@ -321,6 +329,12 @@ int free_all(cc_engine* e)
     e->d_take_ctl = nullptr;
     e->d_take_counts = nullptr;
     e->take_counts_cap = 0;
+    e->d_tc_cursor = nullptr;
+    e->d_tc_plan = nullptr;
+    e->d_tc_table = nullptr;
+    e->d_tc_ctl = nullptr;
+    e->d_tc_slots = nullptr;
+    e->tc_slots_cap = 0;
     e->d_small = nullptr;
     e->d_small_seq = nullptr; // (freed with the allocations above; the pinned counter below goes with it)
     e->d_input_sum = nullptr;
@@ -440,6 +454,8 @@ int reset_state(cc_engine* e, bool keep_table)
     CC_HIP_CHECK(e, hipMemcpyAsync(e->d_states, init.data(), S * sizeof(StreamState), hipMemcpyHostToDevice, e->stream));
     if (e->d_take_cursor) // (cc_engine_take_points: the hand-over starts again with the streams)
         CC_HIP_CHECK(e, hipMemsetAsync(e->d_take_cursor, 0, 2 * S * sizeof(long long), e->stream));
+    if (e->d_tc_cursor) // (cc_engine_take_clusters: ids start at 1 again, the floor at the stream's first column)
+        CC_HIP_CHECK(e, hipMemsetAsync(e->d_tc_cursor, 0, 2 * S * sizeof(long long), e->stream));
     CC_HIP_CHECK(e, hipStreamSynchronize(e->stream));
     for (auto& v : e->pending_events)
         v.clear();
@@ -2362,6 +2378,137 @@ int cc_engine_take_seek(cc_engine* e, int stage, int stream, int64_t column)
     const int first = stream < 0 ? 0 : stream, count = stream < 0 ? e->g.num_streams : 1;
     const std::vector<long long> v((size_t) count, (long long) column);
     CC_HIP_CHECK(e, hipMemcpy(e->d_take_cursor + (size_t) stage * e->g.num_streams + first, v.data(), (size_t) count * sizeof(long long), hipMemcpyHostToDevice));
+    return CC_OK;
+}
+
+// ---- hand-over of the finished clusters in device memory (cc_k_take_clusters.h) -------------------------------------
+// the cursor pairs, the plan, the table and the control block, by the first take (the device blocks again after a change of shape: free_all)
+static int ensure_take_clusters(cc_engine* e)
+{
+    const size_t S = (size_t) e->g.num_streams;
+    int rc;
+    if (!e->h_tc && (rc = alloc_pinned(e, &e->h_tc, S * (sizeof(cck::TcPlan) + sizeof(cc_take_cluster_stream)) + sizeof(cck::TcCtl), PIN_ENGINE)))
+        return rc;
+    if (e->d_tc_cursor)
+        return CC_OK;
+    // (the members are set once all blocks are there, as in ensure_take)
+    long long* cur = nullptr;
+    cck::TcPlan* plan = nullptr;
+    cc_take_cluster_stream* table = nullptr;
+    cck::TcCtl* ctl = nullptr;
+    if ((rc = alloc_plane(e, &cur, 2 * S)) || (rc = alloc_plane(e, &plan, S)) || (rc = alloc_plane(e, &table, S)) || (rc = alloc_plane(e, &ctl, 1)))
+        return rc;
+    CC_HIP_CHECK(e, hipMemsetAsync(cur, 0, 2 * S * sizeof(long long), query_stream(e)));
+    CC_HIP_CHECK(e, hipStreamSynchronize(query_stream(e)));
+    e->d_tc_plan = plan;
+    e->d_tc_table = table;
+    e->d_tc_ctl = ctl;
+    e->d_tc_cursor = cur;
+    return CC_OK;
+}
+
+int cc_engine_take_clusters(cc_engine* e, uint32_t min_points, int flags, cc_take_cluster* d_clusters, int64_t cluster_capacity, cc_take_point* d_records,
+                            int64_t record_capacity, cc_take_cluster_stream* d_table, cc_take_cluster_stream* h_table, int64_t* n_clusters,
+                            int64_t* n_records)
+{
+    if (!e)
+        return CC_ERR_INVALID_ARGUMENT;
+    const bool with_points = flags == CC_TAKE_CLUSTERS_WITH_POINTS;
+    const char* bad = nullptr;
+    if (flags != CC_TAKE_CLUSTERS_WITH_POINTS && flags != CC_TAKE_CLUSTERS_DESCRIPTORS_ONLY)
+        bad = "flags must be CC_TAKE_CLUSTERS_WITH_POINTS or CC_TAKE_CLUSTERS_DESCRIPTORS_ONLY";
+    else if (cluster_capacity < 0 || (!d_clusters && cluster_capacity != 0))
+        bad = "cluster_capacity must be >= 0, and 0 without a descriptor array (the size query)";
+    else if (record_capacity < 0 || (!d_records && record_capacity != 0))
+        bad = "record_capacity must be >= 0, and 0 without a record array";
+    else if (d_clusters && with_points && !d_records)
+        bad = "d_records must not be NULL unless CC_TAKE_CLUSTERS_DESCRIPTORS_ONLY is set";
+    else if (((uintptr_t) d_clusters & 15u) != 0 || ((uintptr_t) d_records & 15u) != 0)
+        bad = "d_clusters and d_records must be 16-byte aligned";
+    else if (((uintptr_t) d_table & 7u) != 0)
+        bad = "d_table must be 8-byte aligned";
+    else if (!h_table || !n_clusters || !n_records)
+        bad = "h_table, n_clusters and n_records must not be NULL";
+    if (bad)
+    {
+        e->error = std::string("cc_engine_take_clusters: ") + bad;
+        return CC_ERR_INVALID_ARGUMENT;
+    }
+    int rc = take_enter(e, "cc_engine_take_clusters", CC_TAKE_CLUSTERED);
+    if (rc || (rc = ensure_take_clusters(e)))
+        return rc;
+    const int S = e->g.num_streams;
+    hipStream_t q = query_stream(e);
+    cck::TcPlan* h_plan = (cck::TcPlan*) e->h_tc;
+    cc_take_cluster_stream* h_tab = (cc_take_cluster_stream*) (e->h_tc + (size_t) S * sizeof(cck::TcPlan));
+    cck::TcCtl* h_ctl = (cck::TcCtl*) (e->h_tc + (size_t) S * (sizeof(cck::TcPlan) + sizeof(cc_take_cluster_stream)));
+    hipLaunchKernelGGL(cck::k_tc_plan, dim3(1), dim3(cck::TAKE_SCAN_THREADS), 0, q, e->g, e->d_states, e->d_tc_cursor, e->d_tc_plan, e->d_tc_table, h_plan, h_ctl);
+    CC_HIP_CHECK(e, hipGetLastError());
+    CC_HIP_CHECK(e, hipStreamSynchronize(q));
+    // the grids follow the plan: the longest column range, the longest id range, the ids of all streams
+    int64_t longest_cols = 0, longest_ids = 0;
+    for (int s = 0; s < S; s++)
+    {
+        longest_cols = std::max<int64_t>(longest_cols, h_plan[s].col_to - h_plan[s].col_from);
+        longest_ids = std::max<int64_t>(longest_ids, h_plan[s].n_ids);
+    }
+    const int64_t total_ids = h_ctl->total_ids;
+    if (longest_cols > e->g.ring_cols || total_ids < 0 || total_ids + S > 0x7fffffffll)
+    {
+        e->error = "cc_engine_take_clusters: a range longer than the ring, or more ids than a grid has blocks";
+        return CC_ERR_BOOKKEEPING;
+    }
+    // (twice what is needed: id counts that creep up from take to take must not allocate a new block each time)
+    const size_t slots_need = (size_t) std::max<int64_t>(total_ids, 1);
+    if ((rc = grow_scratch(e, &e->d_tc_slots, &e->tc_slots_cap, slots_need, 2 * slots_need)))
+        return rc;
+    if (total_ids > 0)
+    {
+        hipLaunchKernelGGL(cck::k_tc_clear, dim3((unsigned) ((longest_ids + cck::TAKE_SCAN_THREADS - 1) / cck::TAKE_SCAN_THREADS), (unsigned) S),
+                           dim3(cck::TAKE_SCAN_THREADS), 0, q, e->d_tc_plan, e->d_tc_slots, (long long) total_ids);
+        if (longest_cols > 0)
+            hipLaunchKernelGGL(cck::k_tc_mark, dim3((unsigned) longest_cols, (unsigned) S), dim3(64), 0, q, e->g, e->P, e->d_tc_plan, e->d_tc_table,
+                               e->d_tc_slots, (long long) total_ids);
+    }
+    hipLaunchKernelGGL(cck::k_tc_scan, dim3((unsigned) S), dim3(cck::TAKE_SCAN_THREADS), 0, q, e->d_tc_plan, e->d_tc_table, e->d_tc_slots, (long long) total_ids,
+                       (unsigned) min_points);
+    hipLaunchKernelGGL(cck::k_tc_scan_streams, dim3(1), dim3(cck::TAKE_SCAN_THREADS), 0, q, S, e->d_tc_table, (long long) cluster_capacity,
+                       (long long) record_capacity, d_clusters ? 1 : 0, with_points ? 1 : 0, (long long) total_ids, e->d_tc_ctl, d_table, h_tab, h_ctl);
+    if (d_clusters) // (the kernel looks at the verdict itself: nothing is written and no cursor moves unless everything fits)
+        hipLaunchKernelGGL(cck::k_tc_write, dim3((unsigned) (S + total_ids)), dim3(64), 0, q, e->g, e->P, e->d_tc_plan, e->d_tc_table, e->d_tc_ctl, e->d_tc_slots,
+                           (long long) total_ids, d_clusters, with_points ? d_records : nullptr, e->d_tc_cursor);
+    CC_HIP_CHECK(e, hipGetLastError());
+    CC_HIP_CHECK(e, hipStreamSynchronize(q));
+    memcpy(h_table, h_tab, (size_t) S * sizeof(cc_take_cluster_stream));
+    *n_clusters = h_ctl->clusters;
+    *n_records = h_ctl->records;
+    if (h_ctl->clusters > cluster_capacity || (with_points && h_ctl->records > record_capacity))
+    {
+        e->error = "cc_engine_take_clusters: " + std::to_string(h_ctl->clusters) + " clusters with " + std::to_string(h_ctl->records) +
+                   " records do not fit capacities of " + std::to_string(cluster_capacity) + " and " + std::to_string(record_capacity) +
+                   " (nothing was written, no cursor moved)";
+        return CC_ERR_CAPACITY;
+    }
+    return CC_OK;
+}
+
+int cc_engine_take_clusters_cursor(cc_engine* e, int stream, int64_t* next_id, int64_t* floor_column, int64_t* readable_from)
+{
+    if (!e || stream < 0 || stream >= e->g.num_streams)
+        return CC_ERR_INVALID_ARGUMENT;
+    int rc = take_enter(e, "cc_engine_take_clusters_cursor", CC_TAKE_CLUSTERED);
+    if (rc || (rc = ensure_take_clusters(e)))
+        return rc;
+    long long cur[2] = {0, 0};
+    StreamState st;
+    CC_HIP_CHECK(e, hipMemcpy(cur, e->d_tc_cursor + 2 * (size_t) stream, sizeof(cur), hipMemcpyDeviceToHost));
+    CC_HIP_CHECK(e, hipMemcpy(&st, e->d_states + stream, sizeof(st), hipMemcpyDeviceToHost));
+    if (next_id)
+        *next_id = cur[0] + 1;
+    if (floor_column)
+        *floor_column = std::max<int64_t>(cur[1], std::max<int64_t>(0, st.first_column));
+    if (readable_from)
+        *readable_from = std::max<int64_t>(0, std::max(st.clear_done, st.first_column));
     return CC_OK;
 }
 

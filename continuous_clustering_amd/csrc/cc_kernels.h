@@ -18,6 +18,7 @@
 //   cc_assocb.h          k_assocb: batch-parallel association + finished-cluster check (groups of columns, pipelined, points packed into lanes)
 //   cc_k_publish.h       k_publish, k_small_tail, frame scatter, cluster gathering, host view
 //   cc_k_take.h          k_take_plan / count / scan / write: the published points of all streams, compacted in device memory
+//   cc_k_take_clusters.h k_tc_plan / clear / mark / scan / write: the finished clusters of all streams, descriptors and grouped points in device memory
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -42,5 +43,6 @@ using namespace ccd;
 #include "cc_assocb.h"
 #include "cc_k_publish.h"
 #include "cc_k_take.h"
+#include "cc_k_take_clusters.h"
 
 } // namespace cck

@@ -332,6 +332,59 @@ int cc_engine_take_cursor(cc_engine* e, int stage, int stream, int64_t* cursor, 
 /* Set the cursor of (stage, stream), stream = -1: of every stream, to `column` (>= 0): skip ahead, or hand columns over again. */
 int cc_engine_take_seek(cc_engine* e, int stage, int stream /* -1: all */, int64_t column);
 
+/* ---- device-to-device hand-over of the clusters finished since the last hand-over, all streams at once ----
+ * The reference's main output: finished_cluster_callback_(cluster_points, stamp) (cc.cpp:1023-1032), without events and without waiting for
+ * the cluster's columns to be published. Cluster ids are a counter (cc.cpp:939), so the clusters finished since a moment are the ids
+ * [next_id, cluster_counter) of the stream; the engine keeps (next_id, floor) per stream in device memory: next_id = 1 and floor = the
+ * stream's first column after create and after cc_engine_reset, independent of the cursors of cc_engine_take_points. A take looks at those ids
+ * in the columns [max(floor, columns cleared already, first column), first_unfinished) and hands over every cluster that has at least `min_points`
+ * members there (the reference's callback threshold is 21; anything <= 6 means every cluster that got an id): one descriptor per cluster,
+ * ordered by stream, then id, and - unless CC_TAKE_CLUSTERS_DESCRIPTORS_ONLY - its members as cc_take_point records with `id` set and
+ * `column` = global column - the CLUSTER's col_from, grouped by descriptor in that order, (column, row) inside a cluster, no gaps. When
+ * everything fits, next_id moves to cluster_counter and floor to the stream's first_unpublished: clusters below `min_points` are consumed too.
+ * n_points counts what the ring holds at take time: for a cluster the reference force-finishes because it exceeds one rotation
+ * (cc.cpp:913-919) it may differ from CC_EV_CLUSTER.d if points join it later. Time stamps stay on the host: firing_min / firing_max are the
+ * keys of the reference's stamp_cluster (cc.cpp:1025-1028) into the caller's own record of firing stamps; like
+ * cc_take_point::source_firing they are the low 32 bits of the firing index, so they wrap after 2^32 firings of a stream. */
+typedef struct cc_take_cluster {          /* 64 bytes */
+    int32_t  stream;
+    uint32_t id;                          /* reference numbering */
+    int64_t  col_from;                    /* first global column (CC_EV_CLUSTER.a) */
+    int64_t  first_record;                /* into d_records */
+    uint32_t n_points, n_columns;         /* CC_EV_CLUSTER.d; last column = col_from + n_columns - 1 (= .b) */
+    uint32_t firing_min, firing_max;      /* min / max of the members' cc_take_point::source_firing (low 32 bits: wraps after 2^32 firings) */
+    float    min_x, min_y, min_z, max_x, max_y, max_z;   /* odom frame */
+} cc_take_cluster;
+
+typedef struct cc_take_cluster_stream {   /* 56 bytes, one per stream */
+    int64_t id_from, id_to;               /* ids [id_from, id_to) were examined; id_to = cluster_counter */
+    int64_t lost_columns;                 /* columns between the floor and what had been cleared already: clusters (or parts) there are gone */
+    int64_t first_record, n_records;      /* this stream's slice of d_records */
+    int32_t first_cluster, n_clusters;    /* this stream's slice of d_clusters */
+    int32_t error;                        /* the stream's CC_ERR_* (then nothing is handed over and its cursor stays) */
+    int32_t pad;
+} cc_take_cluster_stream;
+
+enum { CC_TAKE_CLUSTERS_WITH_POINTS = 0, CC_TAKE_CLUSTERS_DESCRIPTORS_ONLY = 1 };
+
+/* Take. d_clusters: device, `cluster_capacity` descriptors, 16-byte aligned; d_records: device, `record_capacity` records, 16-byte aligned
+ * (may be NULL with CC_TAKE_CLUSTERS_DESCRIPTORS_ONLY: no record is written then, first_record / n_points describe the layout the records
+ * would have, and record_capacity is not looked at). d_table (device, may be NULL) and h_table (host) receive num_streams entries.
+ * Capacity is all or nothing over BOTH arrays: if either is exceeded the call returns CC_ERR_CAPACITY, *n_clusters, *n_records and h_table
+ * say what is needed, nothing is written and no cursor moves - a retry returns what a first call would have. d_clusters == NULL with
+ * cluster_capacity == 0 is the size query: it never moves a cursor (CC_OK when there is nothing to take). If columns above the floor have
+ * been cleared already (no take for most of a ring), lost_columns counts them: clusters wholly inside are dropped, one that straddles the
+ * boundary is handed over with the points that remain (its col_from is then the lowest readable column); nothing is invented. Finishes the
+ * submitted batches first and returns with the output complete. Refused (CC_ERR_INVALID_ARGUMENT) while the option "resident" is on. */
+int cc_engine_take_clusters(cc_engine* e, uint32_t min_points, int flags,
+                            cc_take_cluster* d_clusters, int64_t cluster_capacity,
+                            cc_take_point* d_records, int64_t record_capacity,
+                            cc_take_cluster_stream* d_table /* may be NULL */, cc_take_cluster_stream* h_table /* [num_streams] */,
+                            int64_t* n_clusters, int64_t* n_records);
+/* Of `stream`: the first id the next take examines, the lowest column it looks at unless that has been cleared, and the lowest column that
+ * has not been; any pointer may be NULL. */
+int cc_engine_take_clusters_cursor(cc_engine* e, int stream, int64_t* next_id, int64_t* floor_column, int64_t* readable_from);
+
 /* Engine tuning / test hooks: one option per line, `name` (default) meaning. Values out of range are clamped. Environment variables that override
  * options (CC_ASSOC_ROUNDS, CC_DEFER_TAIL, ... as used by the A/B tools) are only read when CC_ENABLE_ENV_OPTS=1 is set. Every setting gives the
  * same results (the parity tests run over them, tests/test_gpu_stress.py walks random combinations); they only move work between kernels and streams.
