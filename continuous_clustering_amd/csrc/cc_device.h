@@ -26,6 +26,12 @@ constexpr int PP_SKIP = 0x7fffffff;
 #endif
 constexpr int INS_WIN = CC_INS_WIN;          // columns of `distance` kept in LDS by the insertion kernel
 constexpr int SG_NAN = 1, SG_FOG = 2, SG_EGO = 4, SG_INCL_IGNORE = 8, SG_TOO_CLOSE = 16, SG_PENDING = 32; // (k_seg_pre / k_insert_par -> k_seg_scan)
+// A return whose range is NaN (a NaN / inf in its firing's pose: cc.cpp:189, 204-206, 222-238 write such a cell when nothing valid is there, with x, y,
+// z, firing index and a NaN distance; everything behind treats it as a cell without a return, but it is published with those values). Its distance
+// is stored as THIS NaN — a cleared cell holds __builtin_nanf("") or all ones — so that the host view can tell the two apart (view_column: x, y, z,
+// source firing). The segmentation leaves x, y, z of a cell without a return alone for that: nobody else reads them (every reader of a record asks
+// the cell's ignore flag or its distance first).
+constexpr unsigned NAN_RANGE_BITS = 0x7fc00001u;
 #ifndef CC_TREE_SLOTS
 #define CC_TREE_SLOTS 256
 #endif

@@ -34,7 +34,7 @@ __device__ __forceinline__ PreppedPoint prep_point(const float fx, const float f
     o.x = (float) ox;
     o.y = (float) oy;
     o.z = (float) oz;
-    o.dist = dist;
+    o.dist = dist == dist ? dist : __uint_as_float(NAN_RANGE_BITS);
     o.incl = ccm::asinf_exact((float) rz / dist);
     o.incaz = inc_az;
     o.cir = f2i_x86(inc_az / az_width);

@@ -42,7 +42,9 @@ __device__ __forceinline__ void view_column(const Geometry& g, const SP& p, cons
         const bool mine = p.gtag[ci] == tag; // the cell belongs to this pass over the ring (Point::global_column_index == gc)
         const bool filled = in_ring && (segmented ? true : mine);
         const bool has_point = filled && !(p.dist[ci] != p.dist[ci]) && mine;
-        const float4 rec = has_point ? p.sc_rec[ci] : make_float4(nanf_, nanf_, nanf_, nanf_);
+        // a return with a NaN range (cc_device.h: NAN_RANGE_BITS): a cell without a return, except that it shows the x, y, z and the firing it got
+        const bool has_record = has_point || (filled && mine && __float_as_uint(p.dist[ci]) == NAN_RANGE_BITS);
+        const float4 rec = has_record ? p.sc_rec[ci] : make_float4(nanf_, nanf_, nanf_, nanf_);
         o.x[oi] = rec.x;
         o.y[oi] = rec.y;
         o.z[oi] = rec.z;
@@ -52,7 +54,7 @@ __device__ __forceinline__ void view_column(const Geometry& g, const SP& p, cons
         o.caz[oi] = has_point ? cell_caz(cb, p.incaz[ci]) : (segmented ? empty_cell_caz(gc, g.az_width) : __builtin_nan(""));
         o.gcol[oi] = segmented ? gc : (has_point ? gc : -1);
         // (the firing's sequence number, kept as its low 32 bits: it is one of the last 2^32 firings the stream consumed)
-        o.src[oi] = has_point ? (long long) (st->firings_consumed - (unsigned long long) (uint32_t) ((uint32_t) st->firings_consumed - p.src[ci])) : -1;
+        o.src[oi] = has_record ? (long long) (st->firings_consumed - (unsigned long long) (uint32_t) ((uint32_t) st->firings_consumed - p.src[ci])) : -1;
         o.ground[oi] = segmented ? p.ground[ci] : (uint8_t) CC_GP_UNKNOWN;
         o.debug[oi] = segmented ? p.debug[ci] : (uint8_t) CC_DBG_WHITE;
         o.ignored[oi] = segmented ? p.ignored[ci] : 0;

@@ -479,7 +479,7 @@ __global__ __launch_bounds__(64, CC_SEGSCAN_MIN_WAVES_PER_SIMD) void k_seg_scan(
         const float* gz = p.sg_uz + (size_t) lcl * R;
         const float* gw = p.sg_w + (size_t) lcl * R;
         const unsigned char* gf = p.sg_flags + (size_t) lcl * R;
-        float4* g_rec = p.sc_rec + (size_t) lcl * R; // (cells without a return: {NaN, NaN, NaN, supplemented inclination}, what the window scan reads)
+        float4* g_rec = p.sc_rec + (size_t) lcl * R; // (cells without a return: .w = the supplemented inclination, what the window scan reads)
         float* g_incl = p.incl + (size_t) lcl * R;
         const float* tab_in = p.tabc + (size_t) blockIdx.y * R; // the table in front of this tile (wave-uniform: scalar loads)
         unsigned char* oo = l_out + lane * PB;
@@ -588,7 +588,7 @@ __global__ __launch_bounds__(64, CC_SEGSCAN_MIN_WAVES_PER_SIMD) void k_seg_scan(
             const float supp = (supplement & (row < R - 1)) ? (below_nan ? supp_below : wv) + tab : __builtin_nanf("");
             if (is_nan & active)
             {
-                g_rec[row] = make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), supp);
+                g_rec[row].w = supp; // (x, y, z stay: a return with a NaN range is published with them, cc_device.h: NAN_RANGE_BITS)
                 g_incl[row] = supp;
             }
             supp_below = is_nan ? supp : supp_below;
@@ -1145,7 +1145,7 @@ __device__ __forceinline__ void seg_small_body(const Geometry& g, const cc_confi
                 p.gtag[ci] = tag;
             if (is_nan)
             {
-                p.sc_rec[ci] = make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), sincl);
+                p.sc_rec[ci].w = sincl; // (x, y, z stay: a return with a NaN range is published with them, cc_device.h: NAN_RANGE_BITS)
                 p.incl[ci] = sincl;
             }
         }

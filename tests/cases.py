@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import numpy as np
 
+import pose_streams
 import profile_streams
 from continuous_clustering_amd import capi, synth
 from continuous_clustering_amd.synth import Motion, SceneModel, SensorModel
@@ -165,6 +166,8 @@ def ego_case(setting):
 
 
 def build_case(name: str):
+    if name.startswith("o_"):
+        return pose_case(name)
     if name in PROFILE_SENSORS:
         return profile_stream(name), profile_config(name), None
     if name == "p_s64_profiles_moving":
@@ -395,3 +398,61 @@ FIXED_POINT_CASES = ["p_s64_alternating", "p_s64_label_chains"]
 
 # cases stored as golden fixtures under tests/golden/ (inputs + expected outputs)
 GOLDEN_CASES = ["g_s64_translate", "g_s64_forced_finish_ring", "g_s128_offsets", "g_s64_fog_and_ego"]
+
+
+# ---- odometry poses far from the origin, not rigid, not finite (pose_streams.py): o_<what>__<parent or variant>[__<box>] ------------------------
+# tests/test_pose_cases_cpu.py measures on the oracle what each of them does; tests/test_gpu_pose_parity.py runs the engine on them.
+FAR_PARENTS = ["p_s64_profiles_moving", "p_s128_profiles_moving", "p_s40_profiles", "s64_turn"]                      # under every FAR_OFFSETS entry
+# ... and under one offset. Two of them are not the cases of the same name under the UTM offset (tests/test_pose_cases_cpu.py has the figures):
+# p_s64_alternating's 120 firings look along -x, where UTM coordinates are quantised to 3 cm only, and keep their (x, y) apart (6 identical pairs),
+# so it takes the 2^24 offset (1 m); x_s64_refused_attach's wall has no range noise and stands exactly upright, so 14890 vertical pairs share
+# (x, y) before any offset — its wall returns get 0.2 permille of range noise first (x_s64_refused_attach_rough_wall; the posts stay as they are).
+FAR_SINGLE = {"p_s64_alternating": "2p24", "p_s64_label_chains": "utm", "s64_forced_finish_ring": "utm", "x_s64_refused_attach_rough_wall": "utm"}
+FAR_FIXED_POINT_CASES = ["o_2p24__p_s64_alternating", "o_utm__p_s64_label_chains"]
+FAR_CASES = [f"o_{off}__{parent}" for parent in FAR_PARENTS for off in pose_streams.FAR_OFFSETS] + [f"o_{off}__{parent}" for parent, off in FAR_SINGLE.items()]
+
+CORNER_BOXES = ["default", "sensor_ahead_above", "tilted_tf", "asymmetric_box"]
+CORNER_CASES = [f"o_corner__{variant}__{box}" for variant in pose_streams.POSE_VARIANTS for box in CORNER_BOXES]
+
+NON_FINITE_PARENTS = ["s64_turn", "p_s64_profiles_moving"]
+NON_FINITE_CASES = [f"o_{value}_{place}__{parent}" for parent in NON_FINITE_PARENTS for value in ("nan", "inf") for place in pose_streams.NON_FINITE_PLACES]
+
+
+def pose_parent(name):
+    """The case an o_* case was made from."""
+    if name == "p_s128_profiles_moving":
+        return profile_stream("p_s128_profiles", moving=True), profile_config("p_s128_profiles"), None
+    if name == "x_s64_refused_attach_rough_wall":
+        stream, cfg, tf = build_case("x_s64_refused_attach")
+        xyz = stream.xyz.astype(np.float64)
+        wall = np.sqrt((xyz ** 2).sum(-1)) > 30.0
+        factor = 1.0 + np.random.default_rng(481).uniform(-2e-4, 2e-4, wall.shape)
+        xyz[wall] *= factor[wall][:, None]
+        return synth.Stream(xyz=xyz.astype(np.float32), intensity=stream.intensity, poses=stream.poses, sensor=stream.sensor, hit=stream.hit), cfg, tf
+    return build_case(name)
+
+
+def corner_case(variant, box, eps=None, seed=331):
+    """(stream, config, robot_from_sensor, planted): three rotations of 64 x 360 profile columns under the constant pose POSE_VARIANTS[variant], with
+    48 returns planted just inside and just outside the corners of the ego box `box` (pose_streams.plant_box_corners). The margin is 2 permille of the
+    box's half extents; 3 percent for the asymmetric box at UTM coordinates, where with 2 permille the float32 rounding (0.5 m in y) happens to throw
+    every corner of the utm and utm_f32_rotation poses out of the box and the case would hold no EGO return at all."""
+    if eps is None:
+        eps = 3e-2 if box == "asymmetric_box" and variant in pose_streams.UTM_VARIANTS else 2e-3
+    tf, over = (None, {}) if box == "default" else EGO_SETTINGS[box]
+    cfg = profile_config(SWEEP_BASE_CASE, **over)
+    base = profile_streams.make_profile_stream(profile_sensor(SWEEP_BASE_CASE), 3 * 360, seed)
+    stream, planted = pose_streams.plant_box_corners(base, pose_streams.POSE_VARIANTS[variant], tf, cfg, eps)
+    return stream, cfg, tf, planted
+
+
+def pose_case(name):
+    what, _, rest = name[2:].partition("__")
+    if what == "corner":
+        variant, _, box = rest.partition("__")
+        return corner_case(variant, box)[:3]
+    stream, cfg, tf = pose_parent(rest)
+    if what in pose_streams.FAR_OFFSETS:
+        return pose_streams.with_offset(stream, pose_streams.FAR_OFFSETS[what]), cfg, tf
+    value, _, place = what.partition("_")
+    return pose_streams.with_non_finite(stream, {"nan": np.nan, "inf": np.inf}[value], place), cfg, tf
