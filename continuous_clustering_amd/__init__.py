@@ -75,6 +75,7 @@ def load_library():
     L.cc_engine_destroy.restype = None
     L.cc_engine_set_config.argtypes = [vp, C.POINTER(Config)]
     L.cc_engine_reset.argtypes = [vp, i32]
+    L.cc_engine_reset_streams.argtypes = [vp, i32, vp]
     L.cc_engine_set_robot_from_sensor.argtypes = [vp, i32, vp]
     L.cc_engine_add_firings.argtypes = [vp, i32, i64, vp, vp, vp]
     L.cc_engine_add_firings_device.argtypes = [vp, i64, vp, vp, vp]
@@ -158,9 +159,21 @@ class Engine:
         self._check(self.L.cc_engine_set_config(self.h, C.byref(self.cfg)))
 
     def reset(self, num_rows: int | None = None):
+        """``ContinuousClustering::reset(num_rows)`` for all streams (another ``num_rows`` re-shapes the engine). The robot transform is gone
+        afterwards, as in the reference: call ``set_robot_from_sensor`` again."""
         if num_rows is not None:
             self.num_rows = num_rows
         self._check(self.L.cc_engine_reset(self.h, self.num_rows))
+
+    def reset_streams(self, streams):
+        """``reset`` for single streams of a multi-stream engine, an int or an iterable of ints: afterwards each of them is what ``reset()``
+        makes of a stream (ring cleared, counters and cluster ids from the start, error and ``reset_required`` cleared, take cursors at 0,
+        queued events dropped, the inclination table kept, the robot transform gone: call ``set_robot_from_sensor(tf, stream=s)`` again), and
+        no other stream notices. Waits for what is in flight, like ``reset``; duplicates are harmless, an empty list does nothing."""
+        if isinstance(streams, (int, np.integer)):
+            streams = [streams]
+        idx = np.ascontiguousarray(list(streams), dtype=np.int32)
+        self._check(self.L.cc_engine_reset_streams(self.h, len(idx), idx.ctypes.data if len(idx) else None))
 
     def set_robot_from_sensor(self, tf12, stream: int = -1):
         tf = np.ascontiguousarray(tf12, dtype=np.float64).reshape(12)

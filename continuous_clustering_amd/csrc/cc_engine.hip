@@ -406,6 +406,30 @@ int allocate(cc_engine* e)
     return CC_OK;
 }
 
+// A stream as reset(num_rows) leaves it (cc.cpp:28-63): what reset_state stores for every stream and k_reset_streams for the listed ones.
+void fresh_stream_state(const cc_engine* e, StreamState* out)
+{
+    StreamState& st = *out;
+    memset(&st, 0, sizeof(st));
+    st.prev_rearmost = 0;
+    st.prev_foremost = -1;
+    st.first_unfinished = -1;
+    st.ring_start = -1;
+    st.ring_end = -1;
+    st.first_column = -1;
+    st.clear_done = -1;
+    st.first_unpublished = -1;
+    st.cluster_counter = 1;
+    st.min_required = 0;
+    st.finish_lower_bound = std::numeric_limits<double>::max();
+    st.last_round_min_az = -1.0; // Point::visited_at_continuous_azimuth_angle{-1.} cc.hpp:158
+    st.overrun_col = std::numeric_limits<int64_t>::max();
+    st.n_links = 0;
+    for (auto& d : st.batch)
+        d.seg_begin = d.seg_end = d.acp_next = d.pub_begin = d.pub_end = -1, d.mode = 0, d.fused = 0;
+    st.assoc_mode = e->cfg.max_steps_in_row > WIN_COLS - 2 ? 1 : 0;
+}
+
 // reset(num_rows) of every stream, cc.cpp:11-64. `keep_table`: std::vector::resize keeps the old
 // sc_inclination_angles_between_lasers_ values when the size does not change (cc.cpp:46).
 int reset_state(cc_engine* e, bool keep_table)
@@ -431,26 +455,7 @@ int reset_state(cc_engine* e, bool keep_table)
         CC_HIP_CHECK(e, hipMemsetAsync(P.curtab, 0xFF, S * (size_t) g.num_rows * sizeof(float), e->stream));
     std::vector<StreamState> init(S);
     for (auto& st : init)
-    {
-        memset(&st, 0, sizeof(st));
-        st.prev_rearmost = 0;
-        st.prev_foremost = -1;
-        st.first_unfinished = -1;
-        st.ring_start = -1;
-        st.ring_end = -1;
-        st.first_column = -1;
-        st.clear_done = -1;
-        st.first_unpublished = -1;
-        st.cluster_counter = 1;
-        st.min_required = 0;
-        st.finish_lower_bound = std::numeric_limits<double>::max();
-        st.last_round_min_az = -1.0; // Point::visited_at_continuous_azimuth_angle{-1.} cc.hpp:158
-        st.overrun_col = std::numeric_limits<int64_t>::max();
-        st.n_links = 0;
-        for (auto& d : st.batch)
-            d.seg_begin = d.seg_end = d.acp_next = d.pub_begin = d.pub_end = -1, d.mode = 0, d.fused = 0;
-        st.assoc_mode = e->cfg.max_steps_in_row > WIN_COLS - 2 ? 1 : 0;
-    }
+        fresh_stream_state(e, &st);
     CC_HIP_CHECK(e, hipMemcpyAsync(e->d_states, init.data(), S * sizeof(StreamState), hipMemcpyHostToDevice, e->stream));
     if (e->d_take_cursor) // (cc_engine_take_points: the hand-over starts again with the streams)
         CC_HIP_CHECK(e, hipMemsetAsync(e->d_take_cursor, 0, 2 * S * sizeof(long long), e->stream));
@@ -472,6 +477,67 @@ int reset_state(cc_engine* e, bool keep_table)
     e->lazy_miss = 0;
     e->lazy_clean = 0;
     e->lazy_ok = true;
+    return CC_OK;
+}
+
+// reset(num_rows) of the listed streams only, same shape (cc_engine_reset_streams; `list`: sorted, no duplicates, every index checked). Everything
+// reset_state(e, true) does to a stream — the same planes, fill values and StreamState, the stream's rows of curtab kept —, in one launch of
+// k_reset_streams (cc_k_reset.h) instead of ten memsets and a copy per stream. Nothing of the engine is in flight (the caller has drained the chains);
+// returns with the reset complete. What is engine-wide stays: batch_seq, the lazy gate's history, the captured small-call graphs (they bake
+// configuration, geometry and plane pointers; the streams' state they read from d_states).
+int reset_streams_state(cc_engine* e, const std::vector<int>& list)
+{
+    const Geometry& g = e->g;
+    const Planes& P = e->P;
+    const unsigned long long cells = (unsigned long long) g.cells;
+    cck::ResetJob job;
+    memset(&job, 0, sizeof(job));
+    const cck::ResetFill fills[cck::RESET_PLANES] = {
+        {(char*) P.dist, cells * sizeof(float), 0xFF, 0},
+        {(char*) P.incl, cells * sizeof(float), 0xFF, 0},
+        {(char*) P.gtag, cells * sizeof(uint16_t), 0, 0},
+        {(char*) P.id, cells * sizeof(uint32_t), 0, 0},
+        {(char*) P.ground, cells, CC_GP_UNKNOWN, 0},
+        {(char*) P.debug, cells, CC_DBG_WHITE, 0},
+        {(char*) P.ignored, cells, 0, 0},
+        {(char*) P.root, cells * sizeof(int32_t), 0xFF, 0},
+        {(char*) P.tab_acc, (unsigned long long) g.tab_tiles * (unsigned long long) g.num_rows * sizeof(unsigned long long), 0, 0},
+        {(char*) P.sl_ctl, 4 * sizeof(int32_t), 0, 0},
+    };
+    unsigned long long longest = 0;
+    for (int k = 0; k < cck::RESET_PLANES; k++)
+    {
+        job.fill[k] = fills[k];
+        longest = std::max(longest, fills[k].bytes);
+    }
+    fresh_stream_state(e, &job.fresh);
+    job.states = e->d_states;
+    job.take_cursor = e->d_take_cursor;
+    job.tc_cursor = e->d_tc_cursor;
+    job.num_streams = g.num_streams;
+    int rc = ensure_gather(e, list.size() * sizeof(int)); // (scratch of the queries: idle, like everything else of the engine)
+    if (rc)
+        return rc;
+    CC_HIP_CHECK(e, hipMemcpyAsync(e->d_gather, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    // the grid follows the list and the longest slice: a block per RESET_CHUNK_BYTES of it, fewer once the launch would pass RESET_MAX_BLOCKS blocks
+    constexpr size_t MAX_GRID_Y = 65535;
+    for (size_t first = 0; first < list.size(); first += MAX_GRID_Y)
+    {
+        const size_t rows = std::min(MAX_GRID_Y, list.size() - first);
+        const unsigned long long want = (longest + cck::RESET_CHUNK_BYTES - 1) / cck::RESET_CHUNK_BYTES;
+        const unsigned chunks = (unsigned) std::max<unsigned long long>(1, std::min<unsigned long long>(want, (unsigned long long) cck::RESET_MAX_BLOCKS / rows));
+        hipLaunchKernelGGL(cck::k_reset_streams, dim3(chunks, (unsigned) rows), dim3(cck::RESET_THREADS), 0, e->stream, job, (const int*) e->d_gather + first);
+    }
+    CC_HIP_CHECK(e, hipGetLastError());
+    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream));
+    for (int s : list)
+    {
+        e->state_cached[s] = 0;
+        if (s == e->small_view_stream)
+            e->small_view_ok = false;
+        e->pending_events[s].clear();
+        e->pending_links[s].clear();
+    }
     return CC_OK;
 }
 
@@ -1765,6 +1831,47 @@ int cc_engine_reset(cc_engine* e, int num_rows)
     else
         fill_geometry(e, num_rows);
     return reset_state(e, same_shape);
+}
+
+int cc_engine_reset_streams(cc_engine* e, int n, const int* streams)
+{
+    if (!e)
+        return CC_ERR_INVALID_ARGUMENT;
+    if (n == 0)
+        return CC_OK;
+    if (n < 0 || !streams)
+    {
+        e->error = "cc_engine_reset_streams: n must be >= 0 and streams must not be NULL";
+        return CC_ERR_INVALID_ARGUMENT;
+    }
+    for (int i = 0; i < n; i++)
+        if (streams[i] < 0 || streams[i] >= e->g.num_streams)
+        {
+            e->error = "cc_engine_reset_streams: stream " + std::to_string(streams[i]) + " is outside [0, " + std::to_string(e->g.num_streams) + ")";
+            return CC_ERR_INVALID_ARGUMENT;
+        }
+    if (e->cfg.num_columns != e->g.num_columns)
+    {
+        // (the planes of all streams are re-allocated for another number of columns: cc.cpp:14-27)
+        e->error = "cc_engine_reset_streams: the configuration's num_columns waits for a change of shape, which cc_engine_reset applies to all streams";
+        return CC_ERR_INVALID_ARGUMENT;
+    }
+    (void) hipSetDevice(e->device);
+    int rc = stop_resident(e);
+    if (rc)
+        return rc;
+    // what the last pipelined call held back (deferred tail, lazy gate) and the continuation passes behind limit_columns run against the old state,
+    // of the listed streams as of the others; then every chain is waited for
+    rc = finish_batch(e);
+    if (rc)
+        return rc;
+    rc = note_released(e, e->call_seq); // (nothing in flight reads the callers' buffers any more)
+    if (rc)
+        return rc;
+    std::vector<int> list(streams, streams + n);
+    std::sort(list.begin(), list.end());
+    list.erase(std::unique(list.begin(), list.end()), list.end());
+    return reset_streams_state(e, list);
 }
 
 int cc_engine_set_robot_from_sensor(cc_engine* e, int stream, const double tf[12])

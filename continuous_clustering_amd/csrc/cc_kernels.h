@@ -19,6 +19,7 @@
 //   cc_k_publish.h       k_publish, k_small_tail, frame scatter, cluster gathering, host view
 //   cc_k_take.h          k_take_plan / count / scan / write: the published points of all streams, compacted in device memory
 //   cc_k_take_clusters.h k_tc_plan / clear / mark / scan / write: the finished clusters of all streams, descriptors and grouped points in device memory
+//   cc_k_reset.h         k_reset_streams: reset(num_rows) for a list of streams, the other streams untouched
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,5 +45,6 @@ using namespace ccd;
 #include "cc_k_publish.h"
 #include "cc_k_take.h"
 #include "cc_k_take_clusters.h"
+#include "cc_k_reset.h"
 
 } // namespace cck

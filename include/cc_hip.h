@@ -202,6 +202,15 @@ void cc_engine_destroy(cc_engine* e);
 int cc_engine_set_config(cc_engine* e, const cc_config* cfg);
 /* reset(num_rows) (cc.cpp:11-64) for all streams. */
 int cc_engine_reset(cc_engine* e, int num_rows);
+/* reset(num_rows) (cc.cpp:11-64) for the `n` listed streams only, same shape; implies sync. Afterwards every listed stream is what
+ * cc_engine_reset(e, num_rows) makes of a stream: ring cleared, state and counters as after a reset (cluster ids start at 1 again), error and
+ * reset_required cleared, the robot transform gone (set it again: cc_engine_set_robot_from_sensor(e, stream, tf)), the inclination table kept,
+ * its cursors of cc_engine_take_points / cc_engine_take_clusters at 0, its queued events and links dropped. Nothing observable changes for any
+ * other stream. For the front-end of one sensor among many: a jump in time, reset_required, a stream whose `error` is set (such a stream
+ * is skipped by every call until it is reset). One kernel launch whose size follows the list, not the engine. Duplicates are harmless; n == 0
+ * does nothing (and does not synchronise). CC_ERR_INVALID_ARGUMENT, nothing changed: n < 0, streams == NULL, an index outside
+ * [0, num_streams), or a configuration whose num_columns differs from the engine's shape (cc_engine_reset applies that, to all streams). */
+int cc_engine_reset_streams(cc_engine* e, int n, const int* streams);
 /* setTransformRobotFrameFromSensorFrame (cc.cpp:626-631). tf = 3x4 row-major [R|t] in double;
  * stream = -1 sets it for all streams. */
 int cc_engine_set_robot_from_sensor(cc_engine* e, int stream, const double tf[12]);
