@@ -2866,3 +2866,5 @@ const char* cc_engine_last_error(cc_engine* e)
 }
 
 } // extern "C"
+
+#include "cc_replay_eval.h" // the replay evaluator (cc_replay_eval_*, include/cc_kitti.h)

@@ -21,65 +21,19 @@ typedef enum { ncclDouble = 8 } ncclDataType_t;
 #include <vector>
 
 #include "../../include/cc_hip.h"
+#include "cc_eval_shared.h"
 
 namespace
 {
 
-// semantic label ids of KittiLoader::getSemanticKittiLabelNameToLabelNumericMapping (kitti_loader.cpp:566-604) used by
-// KittiEvaluation (kitti_evaluation.cpp:12-27)
-constexpr uint16_t LABEL_UNLABELED = 0, LABEL_ROAD = 40, LABEL_PARKING = 44, LABEL_SIDEWALK = 48, LABEL_OTHER_GROUND = 49,
-                   LABEL_LANE_MARKING = 60, LABEL_TERRAIN = 72;
-constexpr unsigned long long EMPTY = ~0ull;
+using ccev::EMPTY;
+using ccev::Pair;
 
 __global__ __launch_bounds__(256) void k_eval(long long n, const uint16_t* __restrict__ semantic, const uint32_t* __restrict__ euclid,
                                               const uint8_t* __restrict__ is_ground, const uint32_t* __restrict__ detection,
                                               unsigned long long* counts4, unsigned long long* keys, unsigned* vals, unsigned mask)
 {
-    const long long i = (long long) blockIdx.x * 256 + threadIdx.x;
-    unsigned tp = 0, fn = 0, fp = 0, tn = 0;
-    if (i < n)
-    {
-        const uint16_t sl = semantic[i];
-        if (sl != LABEL_UNLABELED) // kitti_evaluation.cpp:49-50
-        {
-            const bool gt_ground = sl == LABEL_LANE_MARKING || sl == LABEL_ROAD || sl == LABEL_PARKING || sl == LABEL_SIDEWALK ||
-                                   sl == LABEL_OTHER_GROUND || sl == LABEL_TERRAIN;
-            const bool seg_ground = is_ground[i] != 0;
-            tp = gt_ground && seg_ground;
-            fn = gt_ground && !seg_ground;
-            fp = !gt_ground && seg_ground;
-            tn = !gt_ground && !seg_ground;
-        }
-        const uint32_t gt = euclid[i], det = detection[i];
-        if (gt != 0 || det != 0) // points with neither label take part in no entropy term (kitti_evaluation.cpp:93-99)
-        {
-            const unsigned long long key = ((unsigned long long) gt << 32) | det;
-            unsigned long long h = key * 0x9E3779B97F4A7C15ull;
-            unsigned slot = (unsigned) (h >> 40) & mask;
-            if (key == EMPTY) // (the one pair that looks like a free slot is counted beside the table)
-                atomicAdd(&counts4[4], 1ull);
-            else
-            while (true)
-            {
-                const unsigned long long old = atomicCAS(&keys[slot], EMPTY, key);
-                if (old == EMPTY || old == key)
-                {
-                    atomicAdd(&vals[slot], 1u);
-                    break;
-                }
-                slot = (slot + 1) & mask;
-            }
-        }
-    }
-    // wave-level reduction of the four counters, one atomic per wave
-    const unsigned long long m_tp = __ballot(tp), m_fn = __ballot(fn), m_fp = __ballot(fp), m_tn = __ballot(tn);
-    if ((threadIdx.x & 63) == 0)
-    {
-        if (m_tp) atomicAdd(&counts4[0], (unsigned long long) __popcll(m_tp));
-        if (m_fn) atomicAdd(&counts4[1], (unsigned long long) __popcll(m_fn));
-        if (m_fp) atomicAdd(&counts4[2], (unsigned long long) __popcll(m_fp));
-        if (m_tn) atomicAdd(&counts4[3], (unsigned long long) __popcll(m_tn));
-    }
+    ccev::eval_point((long long) blockIdx.x * 256 + threadIdx.x, n, semantic, euclid, is_ground, detection, counts4, keys, vals, mask);
 }
 
 __global__ __launch_bounds__(256) void k_eval_compact(unsigned table, const unsigned long long* keys, const unsigned* vals,
@@ -93,11 +47,6 @@ __global__ __launch_bounds__(256) void k_eval_compact(unsigned table, const unsi
         out_vals[o] = vals[i];
     }
 }
-
-struct Pair
-{
-    uint32_t gt, det, n;
-};
 
 } // namespace
 
@@ -113,9 +62,7 @@ int cc_eval_frame_device(int64_t n, const uint16_t* d_semantic, const uint32_t* 
         return CC_OK;
     if (n > (1ll << 30)) // (the table holds at least two slots per point: open addressing never meets a full table)
         return CC_ERR_INVALID_ARGUMENT;
-    unsigned table = 1024;
-    while ((int64_t) table < 2 * n)
-        table <<= 1;
+    const unsigned table = ccev::table_size(n);
     unsigned long long *d_keys = nullptr, *d_counts = nullptr, *d_okeys = nullptr;
     unsigned *d_vals = nullptr, *d_ovals = nullptr, *d_on = nullptr;
     auto fail = [&]()
@@ -158,41 +105,7 @@ int cc_eval_frame_device(int64_t n, const uint16_t* d_semantic, const uint32_t* 
         pairs[i] = Pair{(uint32_t) (hk[i] >> 32), (uint32_t) hk[i], hv[i]};
     if (counts[4])
         pairs.push_back(Pair{0xffffffffu, 0xffffffffu, (unsigned) counts[4]});
-    // over-segmentation entropy (kitti_evaluation.cpp:102-116): ground-truth clusters != 0 in ascending order, inside each the
-    // detections (0 included) in ascending order
-    std::sort(pairs.begin(), pairs.end(), [](const Pair& a, const Pair& b) { return a.gt != b.gt ? a.gt < b.gt : a.det < b.det; });
-    for (size_t i = 0; i < pairs.size();)
-    {
-        size_t j = i;
-        unsigned long long total = 0;
-        while (j < pairs.size() && pairs[j].gt == pairs[i].gt)
-            total += pairs[j++].n;
-        if (pairs[i].gt != 0)
-            for (size_t k = i; k < j; k++)
-            {
-                const double frac = static_cast<double>(pairs[k].n) / static_cast<double>(total);
-                out->over_segmentation_entropy -= frac * std::log(frac);
-            }
-        i = j;
-    }
-    // under-segmentation entropy (kitti_evaluation.cpp:125-145): detections != 0 ascending, inside each the ground-truth labels
-    // (0 included) ascending; a detection that only contains ground truth 0 is skipped
-    std::sort(pairs.begin(), pairs.end(), [](const Pair& a, const Pair& b) { return a.det != b.det ? a.det < b.det : a.gt < b.gt; });
-    for (size_t i = 0; i < pairs.size();)
-    {
-        size_t j = i;
-        unsigned long long total = 0;
-        while (j < pairs.size() && pairs[j].det == pairs[i].det)
-            total += pairs[j++].n;
-        const bool only_unlabeled = (j - i == 1) && pairs[i].gt == 0;
-        if (pairs[i].det != 0 && !only_unlabeled)
-            for (size_t k = i; k < j; k++)
-            {
-                const double frac = static_cast<double>(pairs[k].n) / static_cast<double>(total);
-                out->under_segmentation_entropy -= frac * std::log(frac);
-            }
-        i = j;
-    }
+    ccev::sum_entropies(pairs, out); // (shared with the replay evaluator: cc_eval_shared.h)
     return CC_OK;
 }
 

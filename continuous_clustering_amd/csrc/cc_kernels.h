@@ -20,10 +20,13 @@
 //   cc_k_take.h          k_take_plan / count / scan / write: the published points of all streams, compacted in device memory
 //   cc_k_take_clusters.h k_tc_plan / clear / mark / scan / write: the finished clusters of all streams, descriptors and grouped points in device memory
 //   cc_k_reset.h         k_reset_streams: reset(num_rows) for a list of streams, the other streams untouched
+//   cc_k_replay_eval.h   k_replay_plan / info / walk / scan / apply / eval / compact: frame scatter and label compare of replayed frames, all streams per call
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/cc_kitti.h"
 #include "cc_device.h"
+#include "cc_eval_shared.h"
 #include "cc_math.h"
 
 #pragma clang fp contract(off)
@@ -46,5 +49,6 @@ using namespace ccd;
 #include "cc_k_take.h"
 #include "cc_k_take_clusters.h"
 #include "cc_k_reset.h"
+#include "cc_k_replay_eval.h"
 
 } // namespace cck

@@ -252,6 +252,229 @@ class DeviceFrameScatter:
         self.active[s] = False
 
 
+# ---- the replay evaluator: scatter and evaluation of all streams in one device call (cc_replay_eval_*, include/cc_kitti.h) ----
+REPLAY_ERR_ALREADY_EVALUATED, REPLAY_ERR_TOO_FAR_AHEAD = 101, 102
+REPLAY_ERROR_TEXT = {REPLAY_ERR_ALREADY_EVALUATED: "Found a point belonging to a frame that was already evaluated!",   # kitti_demo.cpp:203-204
+                     REPLAY_ERR_TOO_FAR_AHEAD: "Found a point whose frame is too far ahead!"}                          # kitti_demo.cpp:205-206
+
+
+class EvalFrameResult(C.Structure):
+    """cc_eval_frame_result."""
+    _fields_ = [(n, C.c_double) for n in RESULT_FIELDS]
+
+
+class ReplayRecord(C.Structure):
+    """cc_replay_record."""
+    _fields_ = [("stream", C.c_int32), ("frame", C.c_int32), ("r", EvalFrameResult)]
+
+
+class ReplayStream(C.Structure):
+    """cc_replay_stream."""
+    _fields_ = [("col_from", C.c_int64), ("col_to", C.c_int64), ("lost_columns", C.c_int64), ("error_column", C.c_int64),
+                ("previous_frame", C.c_int32), ("frames_evaluated", C.c_int32), ("error", C.c_int32), ("active", C.c_int32)]
+
+
+EVAL_FRAME_RESULT_DTYPE = np.dtype([(n, "<f8") for n in RESULT_FIELDS])
+REPLAY_RECORD_DTYPE = np.dtype([("stream", "<i4"), ("frame", "<i4"), ("r", EVAL_FRAME_RESULT_DTYPE)])
+REPLAY_STREAM_DTYPE = np.dtype([("col_from", "<i8"), ("col_to", "<i8"), ("lost_columns", "<i8"), ("error_column", "<i8"),
+                                ("previous_frame", "<i4"), ("frames_evaluated", "<i4"), ("error", "<i4"), ("active", "<i4")])
+assert REPLAY_RECORD_DTYPE.itemsize == C.sizeof(ReplayRecord) == 56
+assert REPLAY_STREAM_DTYPE.itemsize == C.sizeof(ReplayStream) == 48
+
+
+def _replay_lib():
+    L = load_library()
+    if not getattr(L, "_replay_eval_ready", False):
+        vp, i32, i64, u64p = C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_uint64)
+        L.cc_replay_eval_create.argtypes = [C.POINTER(vp), vp, i32, i64, i32]
+        L.cc_replay_eval_destroy.argtypes = [vp]
+        L.cc_replay_eval_destroy.restype = None
+        L.cc_replay_eval_original_index.argtypes = [vp, i32, i64]
+        L.cc_replay_eval_original_index.restype = vp
+        L.cc_replay_eval_add_frame.argtypes = [vp, i32, i64, i64, vp, vp]
+        L.cc_replay_eval_set_active.argtypes = [vp, i32, i32]
+        L.cc_replay_eval_seek.argtypes = [vp, i32, i64, C.c_int32]
+        L.cc_replay_eval_step.argtypes = [vp, vp, vp, i64, C.POINTER(i64), vp]
+        L.cc_replay_eval_counters.argtypes = [vp, u64p, u64p, u64p, u64p]
+        L.cc_replay_eval_evaluate_slots.argtypes = [vp, i32, i32, vp, vp]
+        L.cc_replay_eval_slot_arrays.argtypes = [vp, i32, i64, C.POINTER(vp), C.POINTER(vp)]
+        L._replay_eval_ready = True
+    return L
+
+
+class ReplayEval:
+    """cc_replay_eval: the handle as it is (create, add_frame, seek, set_active, step, counters). Keeps the engine alive; close() before the
+    engine's."""
+
+    def __init__(self, engine, slots: int, max_points: int, eval_lanes: int):
+        self.L = _replay_lib()
+        self.e = engine
+        self.slots, self.max_points, self.eval_lanes = int(slots), int(max_points), int(eval_lanes)
+        h = C.c_void_p()
+        engine._check(self.L.cc_replay_eval_create(C.byref(h), engine.h, self.slots, self.max_points, self.eval_lanes))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.e, "h", None):  # (an engine that is gone took its stream with it; the handle's memory goes with the process)
+                self.L.cc_replay_eval_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def original_index_ptr(self, s: int, frame: int) -> int:
+        p = self.L.cc_replay_eval_original_index(self.h, s, frame)
+        if not p:
+            raise ValueError(f"no stream {s}")
+        return int(p)
+
+    def slot_arrays(self, s: int, frame: int) -> tuple:
+        """Device pointers (is_ground uint8, detection uint32) of the slot of `frame`, max_points entries each."""
+        g, d = C.c_void_p(), C.c_void_p()
+        self.e._check(self.L.cc_replay_eval_slot_arrays(self.h, s, frame, C.byref(g), C.byref(d)))
+        return int(g.value), int(d.value)
+
+    def add_frame(self, s: int, frame: int, semantic, euclid):
+        sem = np.ascontiguousarray(semantic, dtype=np.uint16)
+        eu = np.ascontiguousarray(euclid, dtype=np.uint32)
+        if sem.shape != eu.shape or sem.ndim != 1:
+            raise ValueError("semantic and euclid must be one-dimensional and equally long")
+        self.e._check(self.L.cc_replay_eval_add_frame(self.h, s, frame, sem.shape[0], sem.ctypes.data, eu.ctypes.data))
+
+    def set_active(self, s: int, active: bool):
+        self.e._check(self.L.cc_replay_eval_set_active(self.h, s, 1 if active else 0))
+
+    def seek(self, s: int, column: int, previous_frame: int):
+        self.e._check(self.L.cc_replay_eval_seek(self.h, s, int(column), int(previous_frame)))
+
+    def step(self, finish=None, capacity: int | None = None):
+        """-> (rc, records [REPLAY_RECORD_DTYPE], needed, table [REPLAY_STREAM_DTYPE]); rc is CC_OK or CC_ERR_CAPACITY, anything else raises.
+        capacity None: room for every frame a step can complete."""
+        S = self.e.num_streams
+        cap = S * (self.slots + 1) if capacity is None else int(capacity)
+        rec = np.zeros(max(cap, 1), dtype=REPLAY_RECORD_DTYPE)
+        table = np.zeros(S, dtype=REPLAY_STREAM_DTYPE)
+        fin = None if finish is None else np.ascontiguousarray(finish, dtype=np.uint8)
+        if fin is not None and fin.shape != (S,):
+            raise ValueError("finish must have one entry per stream")
+        n = C.c_int64(0)
+        rc = self.L.cc_replay_eval_step(self.h, None if fin is None else fin.ctypes.data, rec.ctypes.data if cap else None, cap, C.byref(n),
+                                        table.ctypes.data)
+        from . import capi
+        if rc not in (capi.CC_OK, capi.CC_ERR_CAPACITY):
+            self.e._check(rc)
+        return rc, (rec[: n.value] if rc == capi.CC_OK else rec[:0]), int(n.value), table
+
+    def evaluate_slots(self, s: int, frames) -> np.ndarray:
+        """The label compare alone: the frames' slots as they are, no walk and no apply (tests)."""
+        fr = np.ascontiguousarray(frames, dtype=np.int32)
+        rec = np.zeros(max(len(fr), 1), dtype=REPLAY_RECORD_DTYPE)
+        self.e._check(self.L.cc_replay_eval_evaluate_slots(self.h, s, len(fr), fr.ctypes.data, rec.ctypes.data))
+        return rec[: len(fr)]
+
+    def counters(self) -> dict:
+        v = [C.c_uint64(0) for _ in range(4)]
+        self.e._check(self.L.cc_replay_eval_counters(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("steps", "kernel_launches", "host_syncs", "eval_rounds"), (int(x.value) for x in v)))
+
+
+class BatchedFrameScatter:
+    """DeviceFrameScatter's surface on the replay evaluator: publish() is ONE cc_replay_eval_step for all streams — the columns published
+    since the last call are walked, applied and every completed frame is evaluated on the device, with a number of kernel launches and host
+    synchronisations that does not depend on the number of streams (counters()). Records are bit-equal to DeviceFrameScatter's. finish(s)
+    is a publish() that also evaluates the stream's final frame; publish(finish=[...]) does both in one call."""
+
+    SLOTS = 4  # one frame fed per step + 3 (include/cc_kitti.h)
+
+    def __init__(self, engine, sequence_ids, max_points: int, device: int = 0, rows: int = 64, cols: int = 2200, slots: int | None = None,
+                 eval_lanes: int | None = None):
+        self.e = engine
+        self.seq = list(sequence_ids)
+        S = len(self.seq)
+        if S != engine.num_streams:
+            raise ValueError("one sequence id per stream of the engine")
+        self.S, self.max_points, self.rows, self.cols = S, int(max_points), rows, cols
+        self.slots = int(slots) if slots else self.SLOTS
+        self.h = ReplayEval(engine, self.slots, self.max_points, int(eval_lanes) if eval_lanes else min(S, 16))
+        self.previous_frame = [0] * S
+        self.active = _ActiveFlags(self)
+        self.records = [[] for _ in range(S)]
+        self.last_table = None
+
+    def close(self):
+        self.h.close()
+
+    def original_index_ptr(self, s: int, frame: int) -> int:
+        return self.h.original_index_ptr(s, frame)
+
+    def add_frame(self, s: int, frame: int, semantic, euclid):
+        """Ground truth of frame `frame` of stream s (what kitti_demo.cpp:352-376 loads before the frame is fed)."""
+        if len(semantic) > self.max_points:
+            raise RuntimeError(f"frame with {len(semantic)} points, capacity {self.max_points}")
+        self.h.add_frame(s, frame, semantic, euclid)
+
+    def _step(self, finish=None):
+        rc, rec, _, table = self.h.step(finish=finish)
+        self.last_table = table
+        if rc != 0:
+            raise RuntimeError(self.e.last_error())
+        for r in rec:
+            s = int(r["stream"])
+            self.records[s].append((self.seq[s], int(r["frame"]), *[float(r["r"][n]) for n in RESULT_FIELDS]))
+        for s in range(self.S):
+            self.previous_frame[s] = int(table["previous_frame"][s])
+            self.active._flags[s] = bool(table["active"][s])
+        for s in range(self.S):
+            err = int(table["error"][s])
+            if err in REPLAY_ERROR_TEXT:
+                raise RuntimeError(REPLAY_ERROR_TEXT[err])
+            if err != 0 and self.active._flags[s]:
+                raise RuntimeError(f"stream {s}: engine error {err}")
+            if int(table["lost_columns"][s]) > 0:
+                raise RuntimeError(f"stream {s}: {int(table['lost_columns'][s])} published columns were cleared before they were scattered")
+
+    def publish(self, finish=()):
+        """Scatter and evaluate everything the engine has published since the last call, all active streams, one device call. `finish`:
+        streams whose final frame is evaluated in the same call (kitti_demo.cpp:417-419); they stop scattering."""
+        fin = None
+        if len(finish):
+            fin = np.zeros(self.S, dtype=np.uint8)
+            fin[list(finish)] = 1
+        self._step(fin)
+
+    def finish(self, s):
+        """"also evaluate final frame" (kitti_demo.cpp:417-419) with what has been published by now; the stream stops scattering."""
+        self.publish(finish=(s,))
+
+    def counters(self) -> dict:
+        return self.h.counters()
+
+
+class _ActiveFlags:
+    """scatter.active[s] = flag reaches the device handle (DeviceFrameScatter keeps a plain list)."""
+
+    def __init__(self, owner):
+        self._owner = owner
+        self._flags = [True] * owner.S
+
+    def __getitem__(self, s):
+        return self._flags[s]
+
+    def __setitem__(self, s, v):
+        self._owner.h.set_active(s, bool(v))
+        self._flags[s] = bool(v)
+
+    def __len__(self):
+        return len(self._flags)
+
+    def __iter__(self):
+        return iter(self._flags)
+
+
 def gather_records(records, group=None, capacity: int | None = None) -> np.ndarray:
     """All-gather the per-frame records [(sequence, frame, tp, fn, fp, tn, OSE, USE)] of every rank and return them sorted by
     (sequence, frame) — the order in which the reference's single process would have produced them. Fixed-size padded buffers,

@@ -53,10 +53,16 @@ class Sequence:
         return lab[:, 0].copy(), eu.astype(np.uint32)
 
 
-def replay(root: str, sequences, rank: int = 0, world: int = 1, device: int = 0, max_frames: int | None = None, timing: dict | None = None):
+def replay(root: str, sequences, rank: int = 0, world: int = 1, device: int = 0, max_frames: int | None = None, timing: dict | None = None,
+           scatter: str = "device"):
     """Replay this rank's share of `sequences` concurrently. Returns this rank's records [(sequence, frame, tp, fn, fp, tn, OSE, USE)]
     and a dict of totals. The frame scatter and the label compare run on the GPU (evaluation.DeviceFrameScatter): per step the host reads
-    files, interpolates poses and looks at two integers per published column."""
+    files, interpolates poses and looks at two integers per published column. scatter="batched": evaluation.BatchedFrameScatter instead, one
+    device call per step for the scatter and the evaluation of all streams (same records)."""
+    if scatter not in ("device", "batched"):
+        raise ValueError(f"scatter must be 'device' or 'batched', not {scatter!r}")
+    batched = scatter == "batched"
+    scatter_class = evaluation.BatchedFrameScatter if batched else evaluation.DeviceFrameScatter
     import time
     import torch
     mine = [Sequence(root, s) for i, s in enumerate(sequences) if i % world == rank]
@@ -75,12 +81,14 @@ def replay(root: str, sequences, rank: int = 0, world: int = 1, device: int = 0,
     d_xyz = torch.full((S, kitti.COLS, kitti.ROWS, 3), float("nan"), dtype=torch.float32, device=dev)
     d_int = torch.zeros((S, kitti.COLS, kitti.ROWS), dtype=torch.uint8, device=dev)
     h_pose = np.zeros((S, kitti.COLS, 12), dtype=np.float64)
-    scatter = evaluation.DeviceFrameScatter(engine, [q.index for q in mine], max_points, device=device, rows=kitti.ROWS, cols=kitti.COLS)
+    scatter = scatter_class(engine, [q.index for q in mine], max_points, device=device, rows=kitti.ROWS, cols=kitti.COLS)
     for s, q in enumerate(mine):
         scatter.active[s] = q.has_labels
     frames_done = 0
     records = []
     t_io = t_dev = 0.0
+    publish_ms = []   # per step: the scatter and evaluation alone (tools/replay_eval_cost.py)
+    sync_publish = timing is not None and bool(timing.get("sync_publish"))
     for f in range(n_steps):
         t0 = time.perf_counter()
         batch = []
@@ -107,17 +115,28 @@ def replay(root: str, sequences, rank: int = 0, world: int = 1, device: int = 0,
         engine.add_firings_device(kitti.COLS, d_xyz.data_ptr(), d_int.data_ptr(), d_pose.data_ptr())
         if engine.sync() != 0:
             raise RuntimeError(engine.last_error())
-        scatter.publish()
-        for s, q in enumerate(mine):
-            if scatter.active[s] and f == min(q.n_frames, n_steps) - 1:
-                scatter.finish(s)        # "also evaluate final frame" (kitti_demo.cpp:417-419) with what has been published by now
-                records.extend(scatter.records[s])   # columns the padding rotations flush later belong to no evaluation
+        t_pub = time.perf_counter()
+        # "also evaluate final frame" (kitti_demo.cpp:417-419) with what has been published by now
+        ending = [s for s, q in enumerate(mine) if scatter.active[s] and f == min(q.n_frames, n_steps) - 1]
+        if batched:
+            scatter.publish(finish=ending)   # (the same device call evaluates the final frames)
+        else:
+            scatter.publish()
+            for s in ending:
+                scatter.finish(s)
+        if sync_publish and engine.sync() != 0:   # (the device scatter's last apply is asynchronous; the batched step returns synchronised)
+            raise RuntimeError(engine.last_error())
+        publish_ms.append((time.perf_counter() - t_pub) * 1e3)
+        for s in ending:
+            records.extend(scatter.records[s])   # columns the padding rotations flush later belong to no evaluation
         t2 = time.perf_counter()
         t_io += t1 - t0
         t_dev += t2 - t1
     tot = engine.totals()
     if timing is not None:
-        timing.update(host_io_s=t_io, device_s=t_dev)
+        timing.update(host_io_s=t_io, device_s=t_dev, publish_ms=publish_ms)
+        if batched:
+            timing["counters"] = scatter.counters()
     return records, dict(streams=S, frames=frames_done, cells_published=int(tot["cells_published"]))
 
 

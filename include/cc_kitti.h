@@ -23,6 +23,8 @@
 
 #include <stdint.h>
 
+#include "cc_hip.h" /* cc_eval_frame_result, the CC_ERR_* codes */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -105,6 +107,91 @@ int cc_engine_scatter_info(struct cc_engine* e, int n, const int32_t* streams, c
                            const int32_t* d_original_index, int slots, int32_t* h_min_frame, int32_t* h_max_frame);
 int cc_engine_scatter_apply(struct cc_engine* e, int stream, int64_t from, int64_t to, const int32_t* d_original_index, int slots,
                             uint8_t* d_is_ground, uint32_t* d_detection, int64_t max_points);
+
+/* ---- the same scatter plus the evaluation of the frames it completes, for all streams in one call ----------------------------------------
+ * A replay evaluator is bound to an engine whose streams are fed as above. Per cc_replay_eval_step it takes, for every active stream, the
+ * columns published since the last step (one cursor per stream in device memory, as cc_engine_take_points has them), finds where frames
+ * complete, writes is_ground / detection of the columns' points into the frames' arrays, evaluates every completed frame
+ * (kitti_evaluation.cpp:29-146) and returns one record per frame. The records are bit-equal to cc_engine_scatter_info / _apply +
+ * cc_eval_frame_device driven by the host walk: the integer work runs on the device, the entropies are summed on the host from the exact pair
+ * counts in std::map order with the host's std::log (the code cc_eval_frame_device uses).
+ *
+ * Storage (device memory, owned by the handle, allocated by cc_replay_eval_create; nothing is allocated or freed afterwards):
+ *   original_index [streams][slots][num_columns][num_rows], initialised to -1; semantic, euclid, is_ground, detection
+ *   [streams][slots][max_points]; n_points [streams][slots]; (cursor, previous_frame, active) per stream, cursor and previous_frame starting
+ *   at 0, active at 1; `eval_lanes` evaluation workspaces (a hash table of the power of two >= 2 * max_points slots each, cc_eval_frame_device's
+ *   rule). Frame f of a stream uses slot f % slots.
+ * The caller's rule for `slots`: slots >= frames fed between two steps + 3 (a column is published within a rotation of its insertion, so the
+ * frames previous_frame .. previous_frame + 2 + frames fed are alive at a step). At most `slots` frames of a stream complete per step; a stream
+ * that has more goes on in the next step.
+ *
+ * cc_replay_eval_original_index  where the converter writes cc_kitti_frame::d_original_index of frame `frame` of `stream`.
+ * cc_replay_eval_add_frame       the ground truth of a frame (host arrays of n_points entries) into its slot, the slot's is_ground / detection to
+ *                                zero; enqueued on cc_engine_hip_stream(e) through pinned staging of the handle, no synchronisation of its own
+ *                                (it waits only if all of the handle's staging blocks, one per stream, are still in flight).
+ *                                CC_ERR_INVALID_ARGUMENT: n_points > max_points; frame >= previous_frame + slots (that slot still belongs to a
+ *                                frame that has not been evaluated); frame < 0.
+ * cc_replay_eval_set_active      an inactive stream is not walked (a sequence without labels, a stream that has finished).
+ * cc_replay_eval_seek            sets the cursor and previous_frame of one stream and clears its CC_REPLAY_ERR_*. After cc_engine_reset_streams
+ *                                on a stream that starts another sequence: seek(stream, 0, 0).
+ * cc_replay_eval_step            finishes the submitted batches first. Walks, per active stream without an error, the columns
+ *                                [max(cursor, clear_done, first column), first_unpublished) as addColumnAndEvaluateFrameIfCompleted does: only
+ *                                cells that hold a return and whose original_index is >= 0 count; a segment ends with the first column whose
+ *                                largest frame is previous_frame + 1, then frame previous_frame is complete and previous_frame increments. A
+ *                                segment with a column whose smallest frame is < previous_frame raises CC_REPLAY_ERR_ALREADY_EVALUATED, one
+ *                                with a column whose largest frame is > previous_frame + 1 CC_REPLAY_ERR_TOO_FAR_AHEAD (the reference's two
+ *                                runtime_errors, kitti_demo.cpp:203-206): that segment is not applied, the cursor stays at its first column
+ *                                (error_column), frames completed by earlier segments of the step are still delivered, the stream reports the
+ *                                error in every step until cc_replay_eval_seek, other streams are unaffected. Columns already cleared are
+ *                                counted in lost_columns and read as empty. finish[s] != 0 additionally evaluates previous_frame of stream s
+ *                                with what has been published by now (kitti_demo.cpp:417-419) and makes the stream inactive (ignored for a
+ *                                stream that is inactive or has an error). Records are ordered by stream, then frame. If they exceed `capacity`:
+ *                                CC_ERR_CAPACITY, *n_records and h_table[].frames_evaluated say what is needed, nothing is applied or evaluated,
+ *                                no cursor and no previous_frame moves (h_table[].previous_frame is the unchanged one), and a retry with room
+ *                                returns what a first call would have. More completed frames than eval_lanes are evaluated in
+ *                                ceil(frames / eval_lanes) rounds inside the call. Refused (CC_ERR_INVALID_ARGUMENT) while the option "resident"
+ *                                is on. Returns synchronised.
+ * cc_replay_eval_counters        kernel launches and host synchronisations of the steps so far, beyond what finishing the submitted batches
+ *                                takes. Per step, with L = the longest column range of the plan and R = eval_rounds of the step:
+ *                                    kernel_launches = 3 + (L > 0 ? 2 : 0) + 2 R      (plan, [info], walk, scan, [apply], R x (eval, compact))
+ *                                    host_syncs      = 2 + R                          (after the plan, after the scan, one per round)
+ *                                Neither depends on the number of streams. A step that returns CC_ERR_CAPACITY has R = 0.
+ * Destroy the evaluator before its engine. */
+#define CC_REPLAY_ERR_ALREADY_EVALUATED 101 /* "Found a point belonging to a frame that was already evaluated!" */
+#define CC_REPLAY_ERR_TOO_FAR_AHEAD 102     /* "Found a point whose frame is too far ahead!" */
+
+typedef struct cc_replay_eval cc_replay_eval;
+typedef struct cc_replay_record
+{
+    int32_t stream, frame;
+    cc_eval_frame_result r;
+} cc_replay_record; /* 56 bytes */
+typedef struct cc_replay_stream /* one per stream */
+{
+    int64_t col_from, col_to;   /* columns [col_from, col_to) were scattered in this step */
+    int64_t lost_columns;       /* columns between the cursor and what had been cleared already */
+    int64_t error_column;       /* first column of the segment that raised `error`, else -1 */
+    int32_t previous_frame;     /* after the step (kitti_demo.cpp previous_frame_index) */
+    int32_t frames_evaluated;   /* records of this stream in this step */
+    int32_t error;              /* 0, CC_REPLAY_ERR_ALREADY_EVALUATED, CC_REPLAY_ERR_TOO_FAR_AHEAD, or the stream's CC_ERR_* */
+    int32_t active;
+} cc_replay_stream;
+
+int cc_replay_eval_create(cc_replay_eval** out, struct cc_engine* e, int slots, int64_t max_points, int eval_lanes);
+void cc_replay_eval_destroy(cc_replay_eval* h);
+int32_t* cc_replay_eval_original_index(cc_replay_eval* h, int stream, int64_t frame);
+int cc_replay_eval_add_frame(cc_replay_eval* h, int stream, int64_t frame, int64_t n_points, const uint16_t* semantic, const uint32_t* euclid);
+int cc_replay_eval_set_active(cc_replay_eval* h, int stream, int active);
+int cc_replay_eval_seek(cc_replay_eval* h, int stream, int64_t column, int32_t previous_frame);
+int cc_replay_eval_step(cc_replay_eval* h, const uint8_t* finish, cc_replay_record* records, int64_t capacity, int64_t* n_records,
+                        cc_replay_stream* h_table);
+int cc_replay_eval_counters(cc_replay_eval* h, uint64_t* steps, uint64_t* kernel_launches, uint64_t* host_syncs, uint64_t* eval_rounds);
+/* Test entry: evaluates the frames `frames[i]` of stream `stream` from their slots as they are (no walk, no apply, no cursor moves), in rounds
+ * of eval_lanes, and writes n records. What tests of the batched label compare alone drive, after cc_replay_eval_add_frame and writes to
+ * cc_replay_eval_slot_arrays. Its rounds count like a step's (two launches, one synchronisation, one eval_round each); `steps` stays. */
+int cc_replay_eval_evaluate_slots(cc_replay_eval* h, int stream, int n, const int32_t* frames, cc_replay_record* records);
+/* Device pointers of the slot of frame `frame` of `stream`: is_ground (uint8) and detection (uint32), max_points entries each. */
+int cc_replay_eval_slot_arrays(cc_replay_eval* h, int stream, int64_t frame, uint8_t** d_is_ground, uint32_t** d_detection);
 
 /* ---- host-side pose arithmetic of the same call sites (plain C, no device work) ------------------------------------------ */
 
