@@ -1124,11 +1124,22 @@ void set_kernel_error(cc_engine* e, int stream, StreamState& st)
     e->error = buf;
 }
 
+// Returns whose global column would be negative are dropped and counted (k_insert2: StreamState::error_b, while `error` is 0). The reference
+// indexes its range image with that column (undefined behaviour, cc.cpp:178-181); the oracle drops the return, goes on and leaves this text:
+// so does the engine. The status stays CC_OK, and an earlier text stays, as in the oracle.
+void note_dropped_returns(cc_engine* e, const StreamState& st)
+{
+    if (st.error == 0 && st.error_b > 0 && e->error.empty())
+        e->error = "negative global column index";
+}
+
 int first_stream_error(cc_engine* e, int first_stream, int count)
 {
     std::vector<StreamState> st(count);
     if (hipMemcpy(st.data(), e->d_states + first_stream, count * sizeof(StreamState), hipMemcpyDeviceToHost) != hipSuccess)
         return CC_ERR_HIP;
+    for (int i = 0; i < count; i++)
+        note_dropped_returns(e, st[i]);
     for (int i = 0; i < count; i++)
         if (st[i].error)
         {
@@ -1460,6 +1471,7 @@ int add_firings_small(cc_engine* e, int stream, int64_t n, const float* xyz, con
         return rc ? rc : first_stream_error(e, stream, 1);
     }
     StreamState& st = *e->h_small_state;
+    note_dropped_returns(e, st);
     if (e->g.record_events && st.n_events > 0)
     {
         auto& dst = e->pending_events[stream];

@@ -3,10 +3,13 @@
 Every case is (stream, config, robot_from_sensor or None). Streams are small (seconds for the CPU oracle)."""
 from __future__ import annotations
 
+import zlib
+
 import numpy as np
 
 import pose_streams
 import profile_streams
+import return_streams
 from continuous_clustering_amd import capi, synth
 from continuous_clustering_amd.synth import Motion, SceneModel, SensorModel
 
@@ -168,6 +171,8 @@ def ego_case(setting):
 def build_case(name: str):
     if name.startswith("o_"):
         return pose_case(name)
+    if name.startswith("r_"):
+        return return_case(name)[:3]
     if name in PROFILE_SENSORS:
         return profile_stream(name), profile_config(name), None
     if name == "p_s64_profiles_moving":
@@ -456,3 +461,46 @@ def pose_case(name):
         return pose_streams.with_offset(stream, pose_streams.FAR_OFFSETS[what]), cfg, tf
     value, _, place = what.partition("_")
     return pose_streams.with_non_finite(stream, {"nan": np.nan, "inf": np.inf}[value], place), cfg, tf
+
+
+# ---- degenerate and extreme returns (return_streams.py): r_<class>__<parent> ---------------------------------------------------------------------
+# tests/test_return_cases_cpu.py measures on the oracle what each of them does; tests/test_gpu_return_parity.py runs the engine on them.
+RETURN_BASE_CASE = "p_s64_profiles"
+RETURN_MIXED_PARENT = "w_s64_240x13"
+RETURN_S64_CASES = [f"r_{cls}__{RETURN_BASE_CASE}" for cls in return_streams.ALL_CLASSES]
+RETURN_CCW_CASES = [f"r_{cls}__{RETURN_BASE_CASE}_ccw" for cls in return_streams.ZERO_CLASSES]       # the zeros under the other sensor direction
+# a thinner set on two rows per lane and on rows off the chunk size: one class of every group
+RETURN_THIN_CLASSES = ["zero", "yneg0_xneg", "edge_hi_exact", "edge_straddle", "scaled_1e-42", "scaled_1e36", "all_inf", "z_nan", "y_nan", "dup_firings",
+                       "gap_half_plus", "one_mid"]
+RETURN_S128_CASES = [f"r_{cls}__p_s128_profiles" for cls in RETURN_THIN_CLASSES]
+RETURN_S40_CASES = [f"r_{cls}__p_s40_profiles" for cls in RETURN_THIN_CLASSES]
+RETURN_RING_CASES = [f"r_{cls}__s64_forced_finish_ring" for cls in return_streams.CLUSTER_CLASSES + ("z_nan",)]
+# the infinities under the moving pose: no entry of its rotation block is zero, so inf stays inf (0 * inf = NaN under the static identity pose)
+RETURN_MOVING_CASES = [f"r_{cls}__p_s64_profiles_moving" for cls in return_streams.INF_CLASSES]
+RETURN_MIXED_CASE = f"r_mixed__{RETURN_MIXED_PARENT}"
+RETURN_CASES = (RETURN_S64_CASES + RETURN_CCW_CASES + RETURN_S128_CASES + RETURN_S40_CASES + RETURN_RING_CASES + RETURN_MOVING_CASES +
+                [RETURN_MIXED_CASE])
+
+
+def return_parent(name):
+    """The case an r_* case was made from."""
+    if name == RETURN_BASE_CASE + "_ccw":
+        rows, cols, top, bottom, _, seed = PROFILE_SENSORS[RETURN_BASE_CASE]
+        sen = SensorModel(num_rows=rows, num_columns=cols, incl_top_deg=top, incl_bottom_deg=bottom, clockwise=False)
+        return profile_streams.make_profile_stream(sen, 2 * cols + cols // 4, seed), profile_config(RETURN_BASE_CASE, sensor_is_clockwise=0), None
+    return build_case(name)
+
+
+def return_seed(name):
+    return zlib.crc32(name.encode()) % 100000
+
+
+def return_case(name):
+    """(stream, config, robot_from_sensor, planted mask [firings, rows]) of an r_* case."""
+    cls, _, parent = name[2:].partition("__")
+    stream, cfg, tf = return_parent(parent)
+    if cls == "mixed":
+        stream, mask, _ = return_streams.plant_mixed(stream, return_seed(name))
+    else:
+        stream, mask = return_streams.plant(stream, cls, return_seed(name))
+    return stream, cfg, tf, mask

@@ -131,7 +131,7 @@ def _check_cluster(d, r, what):
     assert (np.diff(key) > 0).all(), what                                          # strictly increasing in (column, row)
     assert r["column"][0] == 0 and r["column"][-1] == d["n_columns"] - 1, what      # counted from the cluster's own first column, to its last
     for f, v in zip(BOX, (r["x"].min(), r["y"].min(), r["z"].min(), r["x"].max(), r["y"].max(), r["z"].max())):
-        assert d[f] == v, (what, f, d[f], v)                                        # (== : -0 equals +0)
+        assert d[f] == v or (np.isnan(d[f]) and np.isnan(v)), (what, f, d[f], v)    # (== : -0 equals +0; a NaN only equals a NaN)
     assert d["firing_min"] == r["source_firing"].min() and d["firing_max"] == r["source_firing"].max(), what
 
 

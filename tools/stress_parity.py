@@ -1,7 +1,10 @@
 """Randomised parity sweep (GPU box): many small scenes with lots of short-lived trees, odd chunkings, both sensors, both
-association kernels. Engine vs oracle through tests/util.run_and_compare. Usage: python tools/stress_parity.py [--thresholds] [n_cases] [seed0]
+association kernels. Engine vs oracle through tests/util.run_and_compare. Usage: python tools/stress_parity.py [--thresholds] [--returns] [n_cases] [seed0]
 --thresholds: every case also takes three entries of the threshold sweep (tests/cases.py: SEGMENTATION_SWEEP, ASSOCIATION_SWEEP), drawn from a
-generator of their own, so that the scenes, chunkings and options of a seed are the same with and without the switch."""
+generator of their own, so that the scenes, chunkings and options of a seed are the same with and without the switch.
+--returns: every case also gets three classes of degenerate returns (tests/return_streams.py: MIXED_CLASSES — zeros, column edges, scaled, infinite,
+partly NaN, duplicates, lone returns, gaps) planted at about 2 % of its returns behind the first rotation, drawn from a generator of their own as well;
+the oracle's error text (a dropped NaN azimuth) must be the engine's."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -12,12 +15,15 @@ from continuous_clustering_amd.synth import Motion, SceneModel
 from oracle import pyoracle
 pyoracle.build()
 
-args = [a for a in sys.argv[1:] if a != "--thresholds"]
+args = [a for a in sys.argv[1:] if a not in ("--thresholds", "--returns")]
 thresholds = "--thresholds" in sys.argv[1:]
+returns = "--returns" in sys.argv[1:]
 n_cases = int(args[0]) if len(args) > 0 else 12
 seed0 = int(args[1]) if len(args) > 1 else 1000
 # (read only with the switch: without it the tool needs nothing of tests/cases.py beyond the sensors and configurations it always used)
 SWEPT = {**cases.SEGMENTATION_SWEEP, **cases.ASSOCIATION_SWEEP} if thresholds else {}
+if returns:  # (likewise: tests/return_streams.py is read only with its switch)
+    import return_streams
 bad = 0
 for i in range(n_cases):
     rng = np.random.default_rng(seed0 + i)
@@ -31,6 +37,13 @@ for i in range(n_cases):
     motion = [Motion.static(), Motion.translate(float(rng.uniform(1, 20))), Motion.turn(8.0, float(rng.uniform(-1, 1)))][int(rng.integers(0, 3))]
     n = cols * int(rng.integers(2, 4)) + int(rng.integers(0, cols))
     stream = synth.make_stream(n, seed=seed0 + 17 * i, sensor=sensor, scene=scene, motion=motion)
+    planted = []
+    if returns:
+        rrng = np.random.default_rng([seed0 + i, 11])
+        # (the edge classes aim whole firings at a column boundary: not with per-laser azimuth offsets)
+        table = [c for c in return_streams.MIXED_CLASSES if not (s128 and c in return_streams.EDGE_CLASSES)]
+        planted = [str(k) for k in rrng.choice(table, size=3, replace=False)]
+        stream = return_streams.plant_mixed(stream, seed0 + i, classes=tuple(planted))[0]
     over = {}
     if rng.random() < 0.3:
         over["max_distance"] = float(rng.choice([0.4, 0.7, 1.2]))
@@ -53,12 +66,16 @@ for i in range(n_cases):
                                     engine_setup=lambda e: (e.set_option("assoc_waves", waves), e.set_option("assoc_batch", batch),
                                                             e.set_option("assoc_rounds", rounds), box.setdefault("e", e)))
         es = summ["engine_state"]
+        if returns:
+            otext = util.run_oracle(stream, cfg)[0].last_error()
+            assert box["e"].last_error() == otext, f"error text: oracle {otext!r} engine {box['e'].last_error()!r}"
         bc = box["e"].batch_counters()
         print(f"case {i:3d} ok: rows {sensor.num_rows} cols {cols} firings {n} objects {scene.n_objects} chunks {chunks} waves {waves} "
               f"clusters {summ['clusters']} serial columns {es['error_b']} batch {batch} rounds {rounds} columns {bc['batch_columns']} "
-              f"bails {bc['batch_bails']} {bc['bail_reasons'][1:7]}" + (f" thresholds {swept}" if thresholds else ""), flush=True)
+              f"bails {bc['batch_bails']} {bc['bail_reasons'][1:7]}" + (f" thresholds {swept}" if thresholds else "") +
+              (f" returns {planted}" if returns else ""), flush=True)
     except AssertionError as ex:
         bad += 1
-        print(f"case {i:3d} FAILED (seed {seed0 + i}{', thresholds ' + str(swept) if thresholds else ''}): {str(ex)[:300]}", flush=True)
+        print(f"case {i:3d} FAILED (seed {seed0 + i}{', thresholds ' + str(swept) if thresholds else ''}{', returns ' + str(planted) if returns else ''}): {str(ex)[:300]}", flush=True)
 print("failures:", bad)
 sys.exit(1 if bad else 0)
