@@ -29,6 +29,7 @@ struct cc_engine
     int device{0};
     Geometry g{};
     cc_config cfg{};
+    int widest_steps_in_row{0}; // the largest max_steps_in_row of any configuration since the last reset: links made under it are still in the ring (k_view's child counts)
     Planes P{};
     StreamState* d_states{nullptr};
     int* d_remaining{nullptr};
@@ -435,6 +436,7 @@ void fresh_stream_state(const cc_engine* e, StreamState* out)
 int reset_state(cc_engine* e, bool keep_table)
 {
     e->small_view_ok = false;
+    e->widest_steps_in_row = e->cfg.max_steps_in_row; // (no link of an earlier configuration is left in the rings)
     std::fill(e->state_cached.begin(), e->state_cached.end(), 0);
     const Geometry& g = e->g;
     const size_t S = (size_t) g.num_streams;
@@ -1675,6 +1677,7 @@ int cc_engine_create(cc_engine** out, int device, int num_streams, int num_rows,
     e->stream = set.s[0], e->stream2 = set.s[1], e->stream3 = set.s[2], e->stream4 = set.s[3], e->stream5 = set.s[4], e->stream6 = set.s[5];
     for_each_event(e, [](hipEvent_t& ev) { (void) hipEventCreateWithFlags(&ev, hipEventDisableTiming); });
     e->cfg = *cfg;
+    e->widest_steps_in_row = cfg->max_steps_in_row;
     e->g.num_streams = num_streams;
     e->g.tree_capacity = 1 << 15;
     e->g.record_events = num_streams == 1 ? 1 : 0;
@@ -1785,6 +1788,7 @@ int cc_engine_set_config(cc_engine* e, const cc_config* cfg)
                             (e->cfg.sensor_is_clockwise != 0) != (cfg->sensor_is_clockwise != 0) ||
                             e->cfg.num_columns != cfg->num_columns; // cc.cpp:69-74
     e->cfg = *cfg;
+    e->widest_steps_in_row = std::max(e->widest_steps_in_row, cfg->max_steps_in_row);
     e->g.max_distance_squared = cfg->max_distance * cfg->max_distance; // cc.cpp:80
     const bool force_global = cfg->max_steps_in_row > WIN_COLS - 2;
     if (need_reset || force_global)
@@ -1833,16 +1837,27 @@ int cc_engine_reset(cc_engine* e, int num_rows)
     const bool same_shape = num_rows == e->g.num_rows && e->cfg.num_columns == e->g.num_columns;
     if (!same_shape)
     {
+        // cc.cpp:46 resizes sc_inclination_angles_between_lasers_ to the new row count: the rows both shapes have keep their values (all of
+        // them when only num_columns changes), further rows start as NaN. The table goes over the re-allocation on the host, per stream.
+        const size_t S = (size_t) e->g.num_streams;
+        const int old_rows = e->g.num_rows, kept_rows = std::min(old_rows, num_rows);
+        std::vector<float> table(S * (size_t) old_rows);
+        CC_HIP_CHECK(e, hipMemcpy(table.data(), e->P.curtab, table.size() * sizeof(float), hipMemcpyDeviceToHost));
         free_all(e);
         fill_geometry(e, num_rows);
         e->g.event_capacity = e->g.record_events ? 3 * (e->g.limit_columns + e->g.num_columns) + 4096 : 1;
         rc = allocate(e);
         if (rc)
             return rc;
+        rc = reset_state(e, false);
+        if (rc)
+            return rc;
+        CC_HIP_CHECK(e, hipMemcpy2D(e->P.curtab, (size_t) num_rows * sizeof(float), table.data(), (size_t) old_rows * sizeof(float),
+                                    (size_t) kept_rows * sizeof(float), S, hipMemcpyHostToDevice));
+        return CC_OK;
     }
-    else
-        fill_geometry(e, num_rows);
-    return reset_state(e, same_shape);
+    fill_geometry(e, num_rows);
+    return reset_state(e, true);
 }
 
 int cc_engine_reset_streams(cc_engine* e, int n, const int* streams)
@@ -2225,7 +2240,8 @@ static int read_ranges(cc_engine* e, int stream, int nr, const int64_t* from, co
     // the optional fields cost a child-count pass and extra copies: only when the caller asked for one of them
     if (!v->number_of_child_points)
         o.nchild = nullptr;
-    int max_back = e->cfg.max_steps_in_row < e->g.ring_cols - 1 ? e->cfg.max_steps_in_row : e->g.ring_cols - 1;
+    // (a parent sits up to max_steps_in_row columns behind its child — of the configuration the link was made under, which set_config may have narrowed since)
+    int max_back = e->widest_steps_in_row < e->g.ring_cols - 1 ? e->widest_steps_in_row : e->g.ring_cols - 1;
     max_back = max_back < 0 ? 0 : (max_back > 255 ? 255 : max_back);
     cck::ViewRanges vr;
     vr.n = nr;

@@ -200,7 +200,9 @@ void cc_engine_destroy(cc_engine* e);
 /* setConfiguration (cc.cpp:66-81): stores the configuration, recomputes max_distance^2 and raises
  * reset_required on every stream when is_single_threaded / sensor_is_clockwise / num_columns change. */
 int cc_engine_set_config(cc_engine* e, const cc_config* cfg);
-/* reset(num_rows) (cc.cpp:11-64) for all streams. */
+/* reset(num_rows) (cc.cpp:11-64) for all streams; another num_rows, or a num_columns that cc_engine_set_config left waiting, re-shapes the
+ * engine. Like the reference's resize (cc.cpp:46) it keeps the ground segmentation's inclination table: the rows the old and the new shape
+ * have in common, per stream (the option "forget_inclination_table" clears it). */
 int cc_engine_reset(cc_engine* e, int num_rows);
 /* reset(num_rows) (cc.cpp:11-64) for the `n` listed streams only, same shape; implies sync. Afterwards every listed stream is what
  * cc_engine_reset(e, num_rows) makes of a stream: ring cleared, state and counters as after a reset (cluster ids start at 1 again), error and

@@ -121,7 +121,10 @@ class Oracle:
         self.L.orc_set_robot_from_sensor(self.h, tf.ctypes.data)
 
     def reset(self, num_rows=None):
-        self.L.orc_reset(self.h, self.num_rows if num_rows is None else num_rows)
+        """``reset(num_rows)`` of the same object (cc.cpp:11-64): it keeps the inclination table's rows that both row counts have."""
+        if num_rows is not None:
+            self.num_rows = int(num_rows)
+        self.L.orc_reset(self.h, self.num_rows)
 
     def set_config(self, cfg: capi.Config):
         self.cfg = cfg.copy()

@@ -40,10 +40,13 @@ def test_the_scene_finishes_clusters_and_publishes_more_than_the_prewarmed_view(
     assert st["first_unpublished_global_column_index"] - max(st["ring_buffer_start_global_column_index"], 0) > 512
 
 
-def _small_calls_and_queries(e, rows, reads):
+def _small_calls_and_queries(e, rows, reads, same_object=None):
     """Feed the scene in small calls; compare events, published columns and gathered clusters with the oracle; then one read of everything
-    that is published. `reads`: read_columns calls made on this engine so far (view_counters counts every one, on one side or the other)."""
+    that is published. `reads`: read_columns calls made on this engine so far (view_counters counts every one, on one side or the other).
+    `same_object`: (oracle, events) of an oracle object that went through the engine's history and then ran this scene, instead of a fresh one."""
     cfg, stream, oracle, eo = _case(rows)
+    if same_object is not None:
+        oracle, eo = same_object
     oracle_clusters = {int(ev["c"]): int(ev["d"]) for ev in eo[eo["type"] == capi.EV_CLUSTER]}
 
     def healthy():
@@ -116,5 +119,13 @@ def test_prewarm_small_calls_growth_and_reshape(oracle_lib):
     e.reset(32)  # another shape: free_all, then allocate
     e.set_robot_from_sensor(IDENTITY_TF)
     assert e.last_error() == "" and e.state()["num_rows"] == 32
-    _small_calls_and_queries(e, 32, reads)
+    # the yardstick of the second scene is an oracle object with the same history: reset(32) keeps the 16 rows of the inclination table that both
+    # shapes have (cc.cpp:46)
+    first, second = _case(16)[1], _case(32)[1]
+    same, rc = util.run_oracle(first, cfg)
+    assert rc == 0
+    same.reset(32)
+    same.set_robot_from_sensor(IDENTITY_TF)
+    assert same.add_firings(second.xyz, second.intensity, second.poses) == 0, same.last_error()
+    _small_calls_and_queries(e, 32, reads, (same, same.drain_events()))
     e.close()

@@ -183,18 +183,22 @@ def test_deliberate_ring_overrun(chunks, oracle_lib):
 
 def test_reshape_engine_between_resets(oracle_lib):
     """reset(num_rows) with a different row count (cc.cpp:11-27 re-sizes the range image): 32 -> 64 -> 128 rows on one engine, fed by
-    single-firing calls (pinned small-call staging is per row count) and by whole rotations."""
+    single-firing calls (pinned small-call staging is per row count) and by whole rotations. The yardstick is ONE oracle object that goes
+    through the same resets: the inclination table keeps the rows two consecutive shapes have in common (cc.cpp:46)."""
     from continuous_clustering_amd import Engine
     from oracle.pyoracle import Oracle
     cfg = capi.Config.kitti()
     cfg.num_columns = 360
     e = Engine(cfg, 32)
+    o = Oracle(cfg, 32)
+    identity = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], dtype=np.float64)
     for rows, n, chunk in ((32, 500, 1), (64, 500, 1), (128, 500, 1), (64, 800, 360), (32, 420, 7)):
         sen = synth.SensorModel(num_rows=rows, num_columns=360)
         st = synth.make_stream(n, seed=rows + n, sensor=sen, motion=synth.Motion.translate())
         e.reset(rows)
-        e.set_robot_from_sensor(np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], dtype=np.float64))
-        o = Oracle(cfg, rows)
+        e.set_robot_from_sensor(identity)
+        o.reset(rows)
+        o.set_robot_from_sensor(identity)
         assert o.add_firings(st.xyz, st.intensity, st.poses) == 0
         eo = o.drain_events()
         got = []

@@ -69,12 +69,13 @@ def _feed_pipelined(e, streams, F, ring=4, calls=None, stats=None):
     return NB, slots
 
 
-def _compare_with_oracles(e, cfg, streams, NB, F, rows=64, tf=None):
+def _compare_with_oracles(e, cfg, streams, NB, F, rows=64, tf=None, oracles=None):
+    """`oracles`: one object per stream that shares the engine's history (its earlier streams and resets) instead of a fresh one; it is fed here."""
     import util
     from oracle.pyoracle import Oracle, IDENTITY_TF
     bad = []
     for s, st in enumerate(streams):
-        o = Oracle(cfg, rows, IDENTITY_TF if tf is None else tf)
+        o = Oracle(cfg, rows, IDENTITY_TF if tf is None else tf) if oracles is None else oracles[s]
         assert o.add_firings(st.xyz[:NB * F], st.intensity[:NB * F], st.poses[:NB * F]) == 0
         so, se = o.state(), e.state(s)
         diff = {k: (so[k], se[k]) for k in util.STATE_FIELDS if so[k] != se[k]}
@@ -164,30 +165,42 @@ def test_random_walk_over_engine_options(oracle_lib):
 def test_reset_without_sync_behind_pipelined_calls(oracle_lib):
     """a pipelined call leaves the chains behind its insertion to the next call (deferred tail, lazy gate); cc_engine_reset
     must put that closure through against the OLD state before it wipes it — same shape and a different number of rows — and the engine must then
-    behave like a new one."""
+    behave like the reference object after reset(num_rows): one oracle object per stream goes through the same streams and resets (it keeps the
+    inclination table, of which the reset into 32 rows keeps the first 32 rows, cc.cpp:46)."""
     from continuous_clustering_amd import Engine, capi, synth, IDENTITY_TF
+    from oracle.pyoracle import Oracle
     cfg = capi.Config.kitti()
     S, F = 24, 1100
     e = Engine(cfg, 64, S)
     e.record_events(False)
     first = [_perturbed(8100 + s) for s in range(S)]
+    oracles = [Oracle(cfg, 64, IDENTITY_TF) for _ in range(S)]
+
+    def oracles_follow(streams, calls, rows=None):
+        for o, st in zip(oracles, streams):
+            assert o.add_firings(st.xyz[:calls * F], st.intensity[:calls * F], st.poses[:calls * F]) == 0
+            o.reset(rows)
+            o.set_robot_from_sensor(IDENTITY_TF)
+
     _feed_pipelined(e, first, F, ring=8, calls=3)  # no synchronisation: the last call's chains are still held back
     e.reset()
     e.set_robot_from_sensor(IDENTITY_TF)
+    oracles_follow(first, 3)
     second = [_perturbed(8200 + s) for s in range(S)]
     NB, _ = _feed_pipelined(e, second, F, ring=8)
     assert e.sync() == 0, e.last_error()
-    bad = _compare_with_oracles(e, cfg, second, NB, F)
+    bad = _compare_with_oracles(e, cfg, second, NB, F, oracles=oracles)
     assert not bad, bad[:3]
     # again, into another shape: the planes are re-allocated (the held-back closure holds the old pointers by value)
     _feed_pipelined(e, first, F, ring=8, calls=2)
     e.reset(32)
     e.set_robot_from_sensor(IDENTITY_TF)
+    oracles_follow(first, 2, rows=32)  # (on top of the second streams, without a reset in between, like the engine)
     sen = synth.SensorModel(num_rows=32, num_columns=2200, incl_top_deg=10.0, incl_bottom_deg=-30.0)
     third = [synth.make_stream(2200 * 2 + 300, seed=8300 + s, sensor=sen, motion=synth.Motion.translate()) for s in range(S)]
     NB, _ = _feed_pipelined(e, third, F, ring=8)
     assert e.sync() == 0, e.last_error()
-    bad = _compare_with_oracles(e, cfg, third, NB, F, rows=32)
+    bad = _compare_with_oracles(e, cfg, third, NB, F, rows=32, oracles=oracles)
     e.close()
     assert not bad, bad[:3]
 

@@ -1,10 +1,13 @@
 """Randomised parity sweep (GPU box): many small scenes with lots of short-lived trees, odd chunkings, both sensors, both
-association kernels. Engine vs oracle through tests/util.run_and_compare. Usage: python tools/stress_parity.py [--thresholds] [--returns] [n_cases] [seed0]
+association kernels. Engine vs oracle through tests/util.run_and_compare. Usage: python tools/stress_parity.py [--thresholds] [--returns] [--reconfigure] [n_cases] [seed0]
 --thresholds: every case also takes three entries of the threshold sweep (tests/cases.py: SEGMENTATION_SWEEP, ASSOCIATION_SWEEP), drawn from a
 generator of their own, so that the scenes, chunkings and options of a seed are the same with and without the switch.
 --returns: every case also gets three classes of degenerate returns (tests/return_streams.py: MIXED_CLASSES — zeros, column edges, scaled, infinite,
 partly NaN, duplicates, lone returns, gaps) planted at about 2 % of its returns behind the first rotation, drawn from a generator of their own as well;
-the oracle's error text (a dropped NaN azimuth) must be the engine's."""
+the oracle's error text (a dropped NaN azimuth) must be the engine's.
+--reconfigure: every case changes its configuration twice in mid-stream and its robot transform once (tests/reconfigure_streams.py: CONFIG_TABLE,
+TRANSFORM_TABLE; the firings and the entries drawn from a generator of their own): set_config / set_robot_from_sensor between two calls, the oracle
+under the same schedule (tests/util.run_schedule_and_compare)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -15,15 +18,18 @@ from continuous_clustering_amd.synth import Motion, SceneModel
 from oracle import pyoracle
 pyoracle.build()
 
-args = [a for a in sys.argv[1:] if a not in ("--thresholds", "--returns")]
+args = [a for a in sys.argv[1:] if a not in ("--thresholds", "--returns", "--reconfigure")]
 thresholds = "--thresholds" in sys.argv[1:]
 returns = "--returns" in sys.argv[1:]
+reconfigure = "--reconfigure" in sys.argv[1:]
 n_cases = int(args[0]) if len(args) > 0 else 12
 seed0 = int(args[1]) if len(args) > 1 else 1000
 # (read only with the switch: without it the tool needs nothing of tests/cases.py beyond the sensors and configurations it always used)
 SWEPT = {**cases.SEGMENTATION_SWEEP, **cases.ASSOCIATION_SWEEP} if thresholds else {}
 if returns:  # (likewise: tests/return_streams.py is read only with its switch)
     import return_streams
+if reconfigure:  # (likewise)
+    import reconfigure_streams
 bad = 0
 for i in range(n_cases):
     rng = np.random.default_rng(seed0 + i)
@@ -61,21 +67,35 @@ for i in range(n_cases):
     batch = 0 if i % 7 == 6 else 1  # the batch-parallel kernel in front (default) or not
     rounds = [0, 2, 1, 3][i % 4]
     box = {}
+    setup = lambda e: (e.set_option("assoc_waves", waves), e.set_option("assoc_batch", batch), e.set_option("assoc_rounds", rounds), box.setdefault("e", e))
+    changed = []
     try:
-        summ = util.run_and_compare(stream, cfg, chunks=chunks, robot_tf=None,
-                                    engine_setup=lambda e: (e.set_option("assoc_waves", waves), e.set_option("assoc_batch", batch),
-                                                            e.set_option("assoc_rounds", rounds), box.setdefault("e", e)))
+        if reconfigure:
+            crng = np.random.default_rng([seed0 + i, 13])
+            at = sorted(int(a) for a in crng.choice(np.arange(cols // 2, n - 1), size=2, replace=False))
+            entries = [str(k) for k in crng.choice(sorted(reconfigure_streams.CONFIG_TABLE), size=2, replace=False)]
+            tf_name = str(crng.choice(sorted(reconfigure_streams.TRANSFORM_TABLE)))
+            maker = cases._vls if s128 else cases._kitti
+            cfgs = [maker(cols, **{**over, **reconfigure_streams.CONFIG_TABLE[k]}) for k in entries]
+            schedule = reconfigure_streams.cut(n, at, [(cfg, None), (cfgs[0], None), (cfgs[1], reconfigure_streams.TRANSFORM_TABLE[tf_name])])
+            changed = list(zip(at, entries, (None, tf_name)))
+            record = util.schedule_oracle_record(stream, schedule)
+            summ = util.run_schedule_and_compare(stream, schedule, chunks, engine_setup=setup, oracle=record)
+            otext = record[0].last_error()
+        else:
+            summ = util.run_and_compare(stream, cfg, chunks=chunks, robot_tf=None, engine_setup=setup)
+            otext = util.run_oracle(stream, cfg)[0].last_error() if returns else None
         es = summ["engine_state"]
         if returns:
-            otext = util.run_oracle(stream, cfg)[0].last_error()
             assert box["e"].last_error() == otext, f"error text: oracle {otext!r} engine {box['e'].last_error()!r}"
         bc = box["e"].batch_counters()
         print(f"case {i:3d} ok: rows {sensor.num_rows} cols {cols} firings {n} objects {scene.n_objects} chunks {chunks} waves {waves} "
               f"clusters {summ['clusters']} serial columns {es['error_b']} batch {batch} rounds {rounds} columns {bc['batch_columns']} "
               f"bails {bc['batch_bails']} {bc['bail_reasons'][1:7]}" + (f" thresholds {swept}" if thresholds else "") +
-              (f" returns {planted}" if returns else ""), flush=True)
+              (f" returns {planted}" if returns else "") + (f" reconfigured {changed}" if reconfigure else ""), flush=True)
     except AssertionError as ex:
         bad += 1
-        print(f"case {i:3d} FAILED (seed {seed0 + i}{', thresholds ' + str(swept) if thresholds else ''}{', returns ' + str(planted) if returns else ''}): {str(ex)[:300]}", flush=True)
+        print(f"case {i:3d} FAILED (seed {seed0 + i}{', thresholds ' + str(swept) if thresholds else ''}{', returns ' + str(planted) if returns else ''}"
+              f"{', reconfigured ' + str(changed) if reconfigure else ''}): {str(ex)[:300]}", flush=True)
 print("failures:", bad)
 sys.exit(1 if bad else 0)
