@@ -232,6 +232,9 @@ struct Geometry
     int32_t scan_cap;        // visits a lane of the packed window scan spends on its point before it hands it to the long-scan list (option "scan_cap")
     int32_t scan_stores_fin; // per LAUNCH (cc_engine.hip sets it in the copy it hands to a batch's window scan and serial association kernels, 0 elsewhere):
                              // 1 = the scan writes Planes::sc_fin and the serial kernels read it, 0 = nobody writes it and they recompute (cell_fin)
+    int32_t publish_ids;     // engine-wide and sticky (cc_engine.hip: start_publishing_ids): 0 until the first cc_engine_output_planes call that asks for the
+                             // id plane, 1 from then on. While 0 nobody writes Planes::id (publish_body returns at once, the pipeline launches no
+                             // k_publish): every other reader takes the id from t_cid[root] itself
 };
 
 } // namespace ccd

@@ -61,8 +61,10 @@ struct cc_engine
     hipStream_t stream2{nullptr}; // table / segmentation / window-scan chain of the pipelined throughput path
     hipStream_t stream3{nullptr}; // association / publish chain of the pipelined throughput path
     hipStream_t stream4{nullptr}; // window-scan stage of the four-stage pipeline (option "pipeline" = 2)
-    hipStream_t stream6{nullptr}; // k_publish of a pipelined batch: off the association chain, which is the longest of the three
+    hipStream_t stream6{nullptr}; // k_publish of a pipelined batch: off the association chain, which is the longest of the three (idle until ids_wanted)
     hipEvent_t ev_pubrdy[4]{};
+    bool ids_wanted{false};       // Planes::id is maintained (Geometry::publish_ids): off at creation, on for good from the first cc_engine_output_planes
+                                  // call that asks for the id plane (start_publishing_ids); resets zero the plane and leave the flag alone
     hipStream_t stream5{nullptr}; // k_prep of the *next* batch: independent of the engine state, so it runs ahead of the insertion chain
     hipEvent_t ev_ins[4]{}, ev_seg[4]{}, ev_assoc[4]{}, ev_segscan[4]{}, ev_prep[4]{};
     hipEvent_t ev_input{};            // option "input_on_engine_stream": recorded on `stream` when a device call arrives
@@ -308,6 +310,7 @@ void fill_geometry(cc_engine* e, int num_rows)
     if (g.scan_cap <= 0)
         g.scan_cap = cck::SCAN_CAP;
     g.scan_stores_fin = 0; // (set per launch: launch_batch)
+    g.publish_ids = e->ids_wanted ? 1 : 0; // (sticky: a reset, of any shape, keeps it)
 }
 
 int free_all(cc_engine* e)
@@ -2647,10 +2650,38 @@ int cc_engine_take_clusters_cursor(cc_engine* e, int stream, int64_t* next_id, i
     return CC_OK;
 }
 
+// The first request for the id plane: from here on every path publishes ids per batch (Geometry::publish_ids), and the plane is brought up to
+// date once for what was published without it. What was held back goes through and every chain is waited for, as in the take functions; the
+// resident kernel and the captured small-call graphs bake the geometry in, so they go, as in cc_engine_set_option.
+static int start_publishing_ids(cc_engine* e)
+{
+    (void) hipSetDevice(e->device);
+    destroy_small_graphs(e);
+    int rc = stop_resident(e);
+    if (rc)
+        return rc;
+    rc = finish_batch(e);
+    if (rc)
+        return rc;
+    e->ids_wanted = true;
+    e->g.publish_ids = 1;
+    hipLaunchKernelGGL(cck::k_publish_backlog, dim3((unsigned) e->g.num_streams, cck::PUBLISH_BLOCKS), dim3(64), 0, e->stream, e->g, e->P,
+                       (const StreamState*) e->d_states);
+    CC_HIP_CHECK(e, hipGetLastError());
+    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream));
+    return CC_OK;
+}
+
 int cc_engine_output_planes(cc_engine* e, int stream, const uint8_t** d_ground_label, const uint32_t** d_cluster_id)
 {
     if (!e || stream < 0 || stream >= e->g.num_streams)
         return CC_ERR_INVALID_ARGUMENT;
+    if (d_cluster_id && !e->ids_wanted)
+    {
+        int rc = start_publishing_ids(e);
+        if (rc)
+            return rc;
+    }
     if (d_ground_label)
         *d_ground_label = e->P.ground + (size_t) stream * e->g.cells;
     if (d_cluster_id)

@@ -139,9 +139,12 @@ struct HostMirror
 };
 
 // cluster ids of the columns the batch published (cc.cpp:1035-1092: what publishing leaves in Point::id), columns by .. ny .. strided
+// (only once somebody has asked for the id plane, Geometry::publish_ids: the views, the takes and the frame scatter read t_cid[root] themselves)
 __device__ __forceinline__ void publish_body(const Geometry& g, const Planes& P, const StreamState* states, const int s, const int slot, const int by,
                                              const int ny)
 {
+    if (!g.publish_ids)
+        return;
     const StreamState* st = &states[s];
     if (st->batch[slot].pub_begin < 0)
         return;
@@ -224,6 +227,37 @@ __global__ __launch_bounds__(64) void k_publish(Geometry g, Planes P, const Stre
         through = (unsigned long long) uniform_i64((long long) through);
         if (through == (unsigned long long) gridDim.x * gridDim.y - 1ull)
             mirror_results(g, P, states, first_stream, hm);
+    }
+}
+
+// k_publish_backlog — the id plane brought up to date for every stream, once, when Geometry::publish_ids turns on (cc_engine_output_planes): the
+// ring slots of the published columns that are still held, [max(clear_done, first_column), first_unpublished), get what view_column shows for
+// them; every other slot keeps what it has. grid = (streams, PUBLISH_BLOCKS), block = 64, lanes = rows.
+// Reading t_cid[root] now instead of when the column was published gives the same value: a published cell's tree is finished, so neither its root
+// nor the root's id changes again. The root's column can fall below clear_done before the cell's column does, but clearing leaves t_cid alone and
+// the root's slot gets a new tenant only a full ring (10 rotations) later, when the cell's own column is long cleared — the same read view_column makes.
+__global__ __launch_bounds__(64) void k_publish_backlog(Geometry g, Planes P, const StreamState* states)
+{
+    const int s = (int) blockIdx.x;
+    const StreamState* st = &states[s];
+    if (st->ring_end < 0 || st->first_column < 0)
+        return;
+    const SP p = stream_ptrs(P, g, s);
+    const int R = g.num_rows, RC = g.ring_cols;
+    long long lo = st->clear_done > st->first_column ? st->clear_done : st->first_column;
+    // (view_column's `segmented`: inside the ring and below first_unfinished; first_unpublished never passes either)
+    long long hi = st->first_unpublished < st->first_unfinished ? st->first_unpublished : st->first_unfinished;
+    hi = hi < st->ring_end + 1 ? hi : st->ring_end + 1;
+    lo = hi - lo > RC ? hi - RC : lo; // (never more than a ring of slots)
+    for (long long gc = lo + blockIdx.y; gc < hi; gc += gridDim.y)
+    {
+        const int lc = (int) (gc % RC);
+        for (int row = lane_id(); row < R; row += 64)
+        {
+            const int ci = lc * R + row;
+            const int r = p.root[ci];
+            p.id[ci] = (r >= 0 && r < (int) g.cells) ? p.t_cid[r] : 0u;
+        }
     }
 }
 
@@ -584,7 +618,9 @@ __global__ __launch_bounds__(64) void k_scatter_apply(Geometry g, Planes P, cons
             {
                 const size_t o = (size_t) (frame % slots) * (size_t) max_points + (size_t) pt;
                 gr[o] = p.ground[ci] == CC_GP_GROUND ? 1 : 0;
-                det[o] = p.id[ci];
+                // (the id as the takes read it, cc_k_take.h: k_take_write — not from Planes::id, which is only kept once a caller has asked for it)
+                const int r = p.root[ci];
+                det[o] = (r >= 0 && r < (int) g.cells) ? p.t_cid[r] : 0u;
             }
         }
     }

@@ -364,7 +364,9 @@ __global__ __launch_bounds__(64) void k_replay_apply(Geometry g, Planes P, const
             {
                 const size_t o = (size_t) (frame % slots) * (size_t) max_points + (size_t) pt;
                 gr[o] = p.ground[ci] == CC_GP_GROUND ? 1 : 0;
-                det[o] = p.id[ci];
+                // (the id as the takes read it, cc_k_take.h: k_take_write — not from Planes::id, which is only kept once a caller has asked for it)
+                const int r = p.root[ci];
+                det[o] = (r >= 0 && r < (int) g.cells) ? p.t_cid[r] : 0u;
             }
         }
     }

@@ -464,22 +464,27 @@ static int publish_and_release(cc_engine* e, const BatchPass& bp, const TailArgs
     // (without the host synchronisation behind k_insert_par nobody else reads the counter of k_assocb's stops: four bytes ride along here)
     if (batch_assoc && !bp.gate && !bp.gate2 && e->h_bail_count && !e->capturing)
         CC_HIP_CHECK(e, hipMemcpyAsync(e->h_bail_count, e->d_bail_count, 3 * sizeof(int), hipMemcpyDeviceToHost, sa));
+    // Nobody has asked for the id plane (Geometry::publish_ids, cc_engine_output_planes): no pass over the published cells. A pipelined batch
+    // then launches nothing here and the events below follow its last association kernel; a captured small call that mirrors its results
+    // through k_publish keeps the mirror — one block, whose publish_body returns at once.
+    const bool ids = e->g.publish_ids != 0;
     // The ids of the published columns only read what the association of THIS batch left behind (tree root of every cell, cluster id
     // at the root cell; neither is touched again before the ring wraps), so in the pipelined mode they are written on a stream of their
     // own and the next batch's association starts without waiting for them.
-    hipStream_t spub = si != sa ? e->stream6 : sa;
+    hipStream_t spub = (si != sa && ids) ? e->stream6 : sa;
     if (spub != sa)
     {
         CC_HIP_CHECK(e, hipEventRecord(e->ev_pubrdy[bp.slot], sa));
         CC_HIP_CHECK(e, hipStreamWaitEvent(spub, e->ev_pubrdy[bp.slot], 0));
     }
-    if (with_publish)
-        hipLaunchKernelGGL(cck::k_publish, dim3((unsigned) bp.count, cck::PUBLISH_BLOCKS), dim3(64), 0, spub, e->g, e->P, e->d_states, bp.first_stream,
-                           bp.slot, e->capture_mirror);
+    if (with_publish && (ids || e->capture_mirror.state))
+        hipLaunchKernelGGL(cck::k_publish, ids ? dim3((unsigned) bp.count, cck::PUBLISH_BLOCKS) : dim3(1), dim3(64), 0, spub, e->g, e->P, e->d_states,
+                           bp.first_stream, bp.slot, e->capture_mirror);
     CC_MARK(EV_PUBLISH, spub); // ev9: publish
     if (si != sa)
     {
-        CC_HIP_CHECK(e, hipEventRecord(e->ev_assoc[bp.slot], spub)); // the batch descriptor slot is free again after its publish
+        // the batch descriptor slot is free again after its publish, or — without one — after its last association kernel: nothing behind that reads the descriptor
+        CC_HIP_CHECK(e, hipEventRecord(e->ev_assoc[bp.slot], spub));
         e->assoc_pending[bp.slot] = true;
         if (bp.rel_seq)
         {

@@ -286,7 +286,14 @@ int cc_engine_read_column_ranges(cc_engine* e, int stream, int n_ranges, const i
 
 /* Device pointers of the two per-cell OUTPUT planes of a stream's ring buffer (ground label u8,
  * cluster id u32), indexed [local_column * num_rows + row] — what the label-compare kernels and
- * bench checksums read without leaving HBM. */
+ * bench checksums read without leaving HBM. Either argument may be NULL.
+ * The ground plane is always current. The id plane is kept current from the FIRST call that asks for it (a non-NULL d_cluster_id, any stream):
+ * until then the engine writes no ids into it — the column views, the takes and the frame scatter read the id from the root of the point's tree
+ * and never needed the copy. That first call waits for everything in flight (like cc_engine_sync), brings the plane up to date for every
+ * published column that is still in the ring, [max(cleared, first column), first unpublished) of every stream, and returns with it readable;
+ * from then on every batch publishes its ids as it completes, for the rest of the engine's life (the pointer stays valid until a reset to another
+ * shape). cc_engine_reset and cc_engine_reset_streams zero the plane's slices and leave the request standing. Slots of columns outside that range
+ * have no defined content. A caller that wants the plane from the first batch asks once right after cc_engine_create. */
 int cc_engine_output_planes(cc_engine* e, int stream, const uint8_t** d_ground_label, const uint32_t** d_cluster_id);
 
 /* Cluster hand-off: the member points of n finished clusters of `stream`, gathered and compacted on the device — the point
