@@ -289,6 +289,7 @@ __device__ __forceinline__ void caz_key(const float packed, int& kpos, int& kneg
 // (Point::global_column_index, cleared to -1: cc.cpp:1110-1119) and compares it with the column being segmented (cc.cpp:320-345). A cell
 // of ring column lc can only ever hold a global column lc + pass * ring_cols, so the pass index says the same in two bytes:
 // 0 = cleared, else 0x8000 | (pass mod 2^15). A stale cell is met (and reported) on the very next pass, long before a tag could repeat.
+// tests/test_gpu_longrun_parity.py runs every user of the tag across pass 32 768, where it goes from 0xFFFF back to 0x8000, against the oracle.
 constexpr uint16_t CELL_CLEARED = 0;
 __device__ __forceinline__ uint16_t cell_tag(const long long pass)
 {

@@ -757,6 +757,10 @@ __device__ __forceinline__ void insert2_body(const Geometry& g, const cc_config&
             first_unf = prev_rear;
             if (seg_begin < 0)
                 seg_begin = first_unf;
+            // the emission limit of the call that starts the stream counts from its first column: without it such a call ran on unlimited,
+            // and one of more than a ring of firings overwrote columns nobody had segmented yet (tests/test_gpu_longrun_parity.py)
+            if (limit_base < 0)
+                limit_base = first_unf;
             if (lane == 0)
                 st->first_column = first_unf;
         }
