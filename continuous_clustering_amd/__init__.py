@@ -19,7 +19,7 @@ from . import capi
 from .capi import Config
 
 __all__ = ["Config", "Engine", "EngineError", "load_library", "capi", "IDENTITY_TF", "take", "TAKE_POINT_DTYPE", "TAKE_STREAM_DTYPE",
-           "TakeCapacityError", "pointcloud2_fields", "TAKE_CLUSTER_DTYPE", "TAKE_CLUSTER_STREAM_DTYPE"]
+           "TakeCapacityError", "pointcloud2_fields", "TAKE_CLUSTER_DTYPE", "TAKE_CLUSTER_STREAM_DTYPE", "poses", "PoseTracks"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.environ.get("CC_HIP_LIB", "libcc_hip.so"))  # (CC_HIP_LIB: another build of the same library, for A/B tools)
@@ -329,3 +329,7 @@ Engine.take_seek = take.take_seek
 Engine.take_clusters = take.take_clusters
 Engine.take_clusters_size = take.take_clusters_size
 Engine.take_clusters_cursor = take.take_clusters_cursor
+
+# ---- per-firing odometry poses interpolated on the device from pose tracks (poses.py) ------------------------------
+from . import poses  # noqa: E402
+from .poses import PoseTracks  # noqa: E402

@@ -5,7 +5,8 @@ the data path), per-frame evaluation records are gathered with one all_gather at
 Per step every live stream advances by one frame: .bin -> cc_kitti_convert_frames (rows, un-correction, range image, pseudo-firings,
 all on the GPU, written straight into the engine's input arrays) -> cc_engine_add_firings_device -> newly published columns are
 scattered back to their frames (kitti_demo.cpp:173-224) -> cc_eval_frame on the GPU when a frame completes. What stays on the host is
-file I/O, the per-firing pose interpolation and the bookkeeping of which cell belongs to which KITTI point.
+file I/O, the per-firing pose interpolation (poses="device": that too is on the GPU, poses.PoseTracks) and the bookkeeping of which cell
+belongs to which KITTI point.
 
     python -m continuous_clustering_amd.replay <root> 0 1 2 ...        # single process
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 -m continuous_clustering_amd.replay <root> 0 1 ...
@@ -18,6 +19,7 @@ import sys
 import numpy as np
 
 from . import Engine, capi, evaluation, kitti
+from . import poses as pose_tracks
 
 NO_POINT = np.uint64(2 ** 64 - 1)
 
@@ -54,13 +56,19 @@ class Sequence:
 
 
 def replay(root: str, sequences, rank: int = 0, world: int = 1, device: int = 0, max_frames: int | None = None, timing: dict | None = None,
-           scatter: str = "device"):
+           scatter: str = "device", poses: str = "host"):
     """Replay this rank's share of `sequences` concurrently. Returns this rank's records [(sequence, frame, tp, fn, fp, tn, OSE, USE)]
     and a dict of totals. The frame scatter and the label compare run on the GPU (evaluation.DeviceFrameScatter): per step the host reads
     files, interpolates poses and looks at two integers per published column. scatter="batched": evaluation.BatchedFrameScatter instead, one
-    device call per step for the scatter and the evaluation of all streams (same records)."""
+    device call per step for the scatter and the evaluation of all streams (same records).
+    poses: where the per-firing poses come from. "host": kitti.firing_stamps_and_poses per stream and step, uploaded. "device": the
+    sequences' poses are set once as pose tracks (poses.PoseTracks) and one sweep per step on the engine's HIP stream writes the poses of all
+    streams where the engine reads them; nothing is interpolated, uploaded or waited for on the host. "twin": the host loop with
+    poses.host_sweep, the exact CPU counterpart of "device" (the two give the same records; "host" differs from them by the libm)."""
     if scatter not in ("device", "batched"):
         raise ValueError(f"scatter must be 'device' or 'batched', not {scatter!r}")
+    if poses not in ("host", "device", "twin"):
+        raise ValueError(f"poses must be 'host', 'device' or 'twin', not {poses!r}")
     batched = scatter == "batched"
     scatter_class = evaluation.BatchedFrameScatter if batched else evaluation.DeviceFrameScatter
     import time
@@ -80,7 +88,15 @@ def replay(root: str, sequences, rank: int = 0, world: int = 1, device: int = 0,
     engine.set_option("input_on_engine_stream", 1)   # the converter writes the engine's inputs on the engine's HIP stream
     d_xyz = torch.full((S, kitti.COLS, kitti.ROWS, 3), float("nan"), dtype=torch.float32, device=dev)
     d_int = torch.zeros((S, kitti.COLS, kitti.ROWS), dtype=torch.uint8, device=dev)
-    h_pose = np.zeros((S, kitti.COLS, 12), dtype=np.float64)
+    if poses != "device":
+        h_pose = np.zeros((S, kitti.COLS, 12), dtype=np.float64)
+    else:
+        tracks = pose_tracks.PoseTracks(S, max(q.n_frames for q in mine), device=device, hip_stream=engine.hip_stream())
+        for s, q in enumerate(mine):
+            tracks.set(s, q.stamps, q.poses)
+        d_pose = torch.empty((S, kitti.COLS, 12), dtype=torch.float64, device=dev)
+        sweep_start, sweep_end = np.zeros(S, dtype=np.uint64), np.zeros(S, dtype=np.uint64)
+        sweep_hold = np.zeros(S, dtype=np.int32)
     scatter = scatter_class(engine, [q.index for q in mine], max_points, device=device, rows=kitti.ROWS, cols=kitti.COLS)
     for s, q in enumerate(mine):
         scatter.active[s] = q.has_labels
@@ -95,8 +111,14 @@ def replay(root: str, sequences, rank: int = 0, world: int = 1, device: int = 0,
         for s, q in enumerate(mine):
             if f < q.n_frames:
                 pts = q.points(f)
-                _, fposes = kitti.firing_stamps_and_poses(q.stamps, q.poses, q.start[f], q.end[f])
-                h_pose[s] = fposes
+                if poses == "host":
+                    _, fposes = kitti.firing_stamps_and_poses(q.stamps, q.poses, q.start[f], q.end[f])
+                    h_pose[s] = fposes
+                elif poses == "twin":
+                    _, fposes = pose_tracks.host_sweep(q.stamps, q.poses, kitti.COLS, q.start[f], q.end[f])
+                    h_pose[s] = fposes
+                else:
+                    sweep_start[s], sweep_end[s], sweep_hold[s] = q.start[f], q.end[f], -1
                 bins = kitti.bin_transforms(q.stamps, q.poses, q.start[f], q.end[f], q.poses[f])
                 if scatter.active[s]:
                     sem, eu = q.labels(f, pts)
@@ -104,12 +126,18 @@ def replay(root: str, sequences, rank: int = 0, world: int = 1, device: int = 0,
                 frames_done += 1
             else:  # this sequence has ended: an empty rotation keeps the stream in step with the others
                 pts, bins = np.zeros((0, 4), np.float32), None
-                h_pose[s] = np.tile(q.poses[q.n_frames - 1], (kitti.COLS, 1))
+                if poses == "device":
+                    sweep_hold[s] = q.n_frames - 1
+                else:
+                    h_pose[s] = np.tile(q.poses[q.n_frames - 1], (kitti.COLS, 1))
             batch.append(dict(points=pts, stages=kitti.ALL_STAGES if bins is not None and len(bins) else kitti.ALL_STAGES & ~kitti.UNDO_EGO_MOTION,
                               start=q.start[min(f, q.n_frames - 1)], end=q.end[min(f, q.n_frames - 1)], bins=bins, d_xyz=d_xyz[s].data_ptr(),
                               d_intensity=d_int[s].data_ptr(), d_original_index=scatter.original_index_ptr(s, f)))
-        d_pose = torch.from_numpy(h_pose).to(dev)
-        torch.cuda.synchronize(dev)                                                     # the pose upload ran on torch's stream
+        if poses == "device":
+            tracks.sweep(kitti.COLS, sweep_start, sweep_end, d_pose, hold=sweep_hold)   # same HIP stream as the engine
+        else:
+            d_pose = torch.from_numpy(h_pose).to(dev)
+            torch.cuda.synchronize(dev)                                                 # the pose upload ran on torch's stream
         t1 = time.perf_counter()
         conv.convert(batch)                                                             # same HIP stream as the engine
         engine.add_firings_device(kitti.COLS, d_xyz.data_ptr(), d_int.data_ptr(), d_pose.data_ptr())
@@ -133,6 +161,8 @@ def replay(root: str, sequences, rank: int = 0, world: int = 1, device: int = 0,
         t_io += t1 - t0
         t_dev += t2 - t1
     tot = engine.totals()
+    if poses == "device":
+        tracks.close()   # before the engine whose stream it uses
     if timing is not None:
         timing.update(host_io_s=t_io, device_s=t_dev, publish_ms=publish_ms)
         if batched:
