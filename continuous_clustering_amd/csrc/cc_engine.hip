@@ -1114,11 +1114,65 @@ void fixup_overrun(cc_engine* e, int stream, StreamState& st)
         }
 }
 
+// CC_ERR_RING_OVERRUN, continued: the columns of the failing call were segmented in parallel, so the table of inclination steps (Planes::curtab,
+// the one thing cc_engine_reset keeps) has taken in the columns behind the stale one as well. The reference threw at the stale column's first
+// cell, in front of its own table update (cc.cpp:337 / :353-357): its table is the one as of the column before. Rebuilt here per row from the
+// last column in front of the stale one in which the row's cell and the cell of the row below both hold a return (the bottom row: its own),
+// going back until every row has one or the columns end that the ring holds for certain (a row without any keeps what the table has).
+void restore_table_after_overrun(cc_engine* e, int stream, const StreamState& st)
+{
+    if (st.error != CC_ERR_RING_OVERRUN || st.overrun_col == std::numeric_limits<int64_t>::max())
+        return;
+    const int R = e->g.num_rows;
+    const int64_t RC = e->g.ring_cols, c = st.overrun_col;
+    const int64_t oldest = std::max<int64_t>(0, c - (RC - 2 * (int64_t) e->g.num_columns));
+    const size_t base = (size_t) stream * (size_t) e->g.cells;
+    float* curtab = e->P.curtab + (size_t) stream * (size_t) R;
+    std::vector<float> table((size_t) R), incl, dist;
+    std::vector<uint16_t> tags;
+    std::vector<uint8_t> found((size_t) R, 0);
+    if (hipMemcpy(table.data(), curtab, (size_t) R * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+        return;
+    int missing = R;
+    for (int64_t hi = c - 1; hi >= oldest && missing > 0;)
+    {
+        const int64_t lo = std::max(std::max(oldest, hi - 255), hi - hi % RC); // (a chunk that does not straddle the ring's end)
+        const size_t n = (size_t) (hi - lo + 1) * (size_t) R, off = base + (size_t) (lo % RC) * (size_t) R;
+        incl.resize(n), dist.resize(n), tags.resize(n);
+        if (hipMemcpy(incl.data(), e->P.incl + off, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(dist.data(), e->P.dist + off, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(tags.data(), e->P.gtag + off, n * sizeof(uint16_t), hipMemcpyDeviceToHost) != hipSuccess)
+            return;
+        for (int64_t g = hi; g >= lo && missing > 0; g--)
+        {
+            const unsigned tag = 0x8000u | ((unsigned) (g / RC) & 0x7fffu);
+            const size_t o = (size_t) (g - lo) * (size_t) R;
+            float below = 0.f; // cc.cpp:309: the walk starts at the bottom row with 0
+            for (int row = R - 1; row >= 0; row--)
+            {
+                const bool has = tags[o + (size_t) row] == tag && !std::isnan(dist[o + (size_t) row]);
+                const float cur = has ? incl[o + (size_t) row] : std::nanf("");
+                const float diff = cur - below;
+                if (!std::isnan(diff) && !found[(size_t) row])
+                {
+                    table[(size_t) row] = diff;
+                    found[(size_t) row] = 1;
+                    missing--;
+                }
+                below = cur;
+            }
+        }
+        hi = lo - 1;
+    }
+    (void) hipMemcpy(curtab, table.data(), (size_t) R * sizeof(float), hipMemcpyHostToDevice);
+}
+
 // Text of a kernel-side error; CC_ERR_RING_OVERRUN carries the reference's wording and numbers (cc.cpp:337-342: stale global column
 // index found in the cell, column being segmented, ring size).
 void set_kernel_error(cc_engine* e, int stream, StreamState& st)
 {
     fixup_overrun(e, stream, st);
+    restore_table_after_overrun(e, stream, st);
     char buf[320];
     if (st.error == CC_ERR_RING_OVERRUN)
         snprintf(buf, sizeof(buf), "stream %d: This column is not cleared (ring buffer full or written after clearing): %lld, %lld, %d", stream,
