@@ -19,7 +19,8 @@ from . import capi
 from .capi import Config
 
 __all__ = ["Config", "Engine", "EngineError", "load_library", "capi", "IDENTITY_TF", "take", "TAKE_POINT_DTYPE", "TAKE_STREAM_DTYPE",
-           "TakeCapacityError", "pointcloud2_fields", "TAKE_CLUSTER_DTYPE", "TAKE_CLUSTER_STREAM_DTYPE", "poses", "PoseTracks"]
+           "TakeCapacityError", "pointcloud2_fields", "TAKE_CLUSTER_DTYPE", "TAKE_CLUSTER_STREAM_DTYPE", "poses", "PoseTracks",
+           "stamps", "FiringStamps", "CLUSTER_STAMP_DTYPE"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.environ.get("CC_HIP_LIB", "libcc_hip.so"))  # (CC_HIP_LIB: another build of the same library, for A/B tools)
@@ -333,3 +334,7 @@ Engine.take_clusters_cursor = take.take_clusters_cursor
 # ---- per-firing odometry poses interpolated on the device from pose tracks (poses.py) ------------------------------
 from . import poses  # noqa: E402
 from .poses import PoseTracks  # noqa: E402
+
+# ---- time stamps of taken points, columns and clusters from a firing-stamp log in device memory (stamps.py) ------
+from . import stamps  # noqa: E402
+from .stamps import CLUSTER_STAMP_DTYPE, FiringStamps  # noqa: E402

@@ -361,8 +361,9 @@ int cc_engine_take_seek(cc_engine* e, int stage, int stream /* -1: all */, int64
  * `column` = global column - the CLUSTER's col_from, grouped by descriptor in that order, (column, row) inside a cluster, no gaps. When
  * everything fits, next_id moves to cluster_counter and floor to the stream's first_unpublished: clusters below `min_points` are consumed too.
  * n_points counts what the ring holds at take time: for a cluster the reference force-finishes because it exceeds one rotation
- * (cc.cpp:913-919) it may differ from CC_EV_CLUSTER.d if points join it later. Time stamps stay on the host: firing_min / firing_max are the
- * keys of the reference's stamp_cluster (cc.cpp:1025-1028) into the caller's own record of firing stamps; like
+ * (cc.cpp:913-919) it may differ from CC_EV_CLUSTER.d if points join it later. The engine carries no time stamps: firing_min / firing_max
+ * are the keys of the reference's stamp_cluster (cc.cpp:1025-1028) into a record of firing stamps, the caller's own or the firing-stamp log
+ * of cc_stamps.h, which resolves the records of a take to point, column and cluster stamps in device memory; like
  * cc_take_point::source_firing they are the low 32 bits of the firing index, so they wrap after 2^32 firings of a stream. */
 typedef struct cc_take_cluster {          /* 64 bytes */
     int32_t  stream;
