@@ -123,9 +123,16 @@ struct StreamState
 struct Planes
 {
     // geometry written by the insertion kernel (x, y, z live in sc_rec below: one 16-byte record per cell)
+    // A cell's inclination has ONE copy: .w of its record sc_rec (below). The record is not cleared when a column is released (the cleared state
+    // of a cell is dist = NaN, gtag = CELL_CLEARED), so a cleared cell, or a cell of an unsegmented column that has received no return yet, still
+    // holds its previous tenant's record. Two readings, and nobody reads .w without one of them:
+    //   raw inclination (k_table, restore_table_after_overrun; k_seg_pre / k_seg_small / the fused insertion read the whole record that way):
+    //       sc_rec.w if gtag is the tag of the current pass over the ring AND dist is not NaN (a return with NAN_RANGE_BITS counts as none:
+    //       its inclination is NaN anyway), else NaN
+    //   published inclination (view_column): sc_rec.w if the cell has a point or its column is segmented, else NaN — every cell of a segmented
+    //       column carries a current-pass record whose .w is the raw or the supplemented inclination
     float* dist;
-    float* incl;
-    float* incaz;     // increasing azimuth angle of the return (cc.cpp:146-148). Its continuous azimuth angle (cc.cpp:184-186) is
+    float* incaz;    // increasing azimuth angle of the return (cc.cpp:146-148). Its continuous azimuth angle (cc.cpp:184-186) is
                       // 2 pi * rotation + incaz, where the rotation is that of the cell's column — or one less when the sign bit is set
                       // (a return moved on to the first column of the next rotation, cc.cpp:188-202)
     uint16_t* gtag;   // which pass over the ring filled the cell (Point::global_column_index in two bytes; 0 = cleared): cc_kernels.h cell_tag

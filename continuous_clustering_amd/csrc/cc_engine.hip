@@ -364,7 +364,7 @@ int allocate(cc_engine* e)
 #define A(field, count)                                \
     if ((rc = alloc_plane(e, &P.field, (count))) != 0) \
         return rc;
-    A(dist, C) A(incl, C) A(incaz, C) A(gtag, C) A(src, C) A(inten, C);
+    A(dist, C) A(incaz, C) A(gtag, C) A(src, C) A(inten, C);
     A(trig, L) A(colg, L) A(colminaz, L);
     A(ground, C) A(debug, C) A(ignored, C) A(root, C) A(id, C);
     A(t_fin, C) A(t_width, C) A(t_pts, C) A(t_uf, C) A(t_cid, C) A(t_pos, C) A(t_finished, C);
@@ -445,9 +445,9 @@ int reset_state(cc_engine* e, bool keep_table)
     const size_t S = (size_t) g.num_streams;
     const size_t C = S * (size_t) g.cells;
     Planes& P = e->P;
-    // cleared cell: distance = inclination = NaN (0xFF bytes), global column index = -1 (tag 0) (cc.cpp:1110-1119)
+    // cleared cell: distance = NaN (0xFF bytes), global column index = -1 (tag 0) (cc.cpp:1110-1119); its inclination is NaN by that
+    // (cc_device.h: Planes::dist)
     CC_HIP_CHECK(e, hipMemsetAsync(P.dist, 0xFF, C * sizeof(float), e->stream));
-    CC_HIP_CHECK(e, hipMemsetAsync(P.incl, 0xFF, C * sizeof(float), e->stream));
     CC_HIP_CHECK(e, hipMemsetAsync(P.gtag, 0, C * sizeof(uint16_t), e->stream));
     CC_HIP_CHECK(e, hipMemsetAsync(P.id, 0, C * sizeof(uint32_t), e->stream));
     CC_HIP_CHECK(e, hipMemsetAsync(P.ground, CC_GP_UNKNOWN, C, e->stream));
@@ -487,7 +487,7 @@ int reset_state(cc_engine* e, bool keep_table)
 
 // reset(num_rows) of the listed streams only, same shape (cc_engine_reset_streams; `list`: sorted, no duplicates, every index checked). Everything
 // reset_state(e, true) does to a stream — the same planes, fill values and StreamState, the stream's rows of curtab kept —, in one launch of
-// k_reset_streams (cc_k_reset.h) instead of ten memsets and a copy per stream. Nothing of the engine is in flight (the caller has drained the chains);
+// k_reset_streams (cc_k_reset.h) instead of nine memsets and a copy per stream. Nothing of the engine is in flight (the caller has drained the chains);
 // returns with the reset complete. What is engine-wide stays: batch_seq, the lazy gate's history, the captured small-call graphs (they bake
 // configuration, geometry and plane pointers; the streams' state they read from d_states).
 int reset_streams_state(cc_engine* e, const std::vector<int>& list)
@@ -499,7 +499,6 @@ int reset_streams_state(cc_engine* e, const std::vector<int>& list)
     memset(&job, 0, sizeof(job));
     const cck::ResetFill fills[cck::RESET_PLANES] = {
         {(char*) P.dist, cells * sizeof(float), 0xFF, 0},
-        {(char*) P.incl, cells * sizeof(float), 0xFF, 0},
         {(char*) P.gtag, cells * sizeof(uint16_t), 0, 0},
         {(char*) P.id, cells * sizeof(uint32_t), 0, 0},
         {(char*) P.ground, cells, CC_GP_UNKNOWN, 0},
@@ -1128,7 +1127,8 @@ void restore_table_after_overrun(cc_engine* e, int stream, const StreamState& st
     const int64_t oldest = std::max<int64_t>(0, c - (RC - 2 * (int64_t) e->g.num_columns));
     const size_t base = (size_t) stream * (size_t) e->g.cells;
     float* curtab = e->P.curtab + (size_t) stream * (size_t) R;
-    std::vector<float> table((size_t) R), incl, dist;
+    std::vector<float> table((size_t) R), dist;
+    std::vector<float4> rec; // (a cell's raw inclination: .w of its record under the cell's tag and distance, cc_device.h: Planes::dist)
     std::vector<uint16_t> tags;
     std::vector<uint8_t> found((size_t) R, 0);
     if (hipMemcpy(table.data(), curtab, (size_t) R * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
@@ -1138,8 +1138,8 @@ void restore_table_after_overrun(cc_engine* e, int stream, const StreamState& st
     {
         const int64_t lo = std::max(std::max(oldest, hi - 255), hi - hi % RC); // (a chunk that does not straddle the ring's end)
         const size_t n = (size_t) (hi - lo + 1) * (size_t) R, off = base + (size_t) (lo % RC) * (size_t) R;
-        incl.resize(n), dist.resize(n), tags.resize(n);
-        if (hipMemcpy(incl.data(), e->P.incl + off, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+        rec.resize(n), dist.resize(n), tags.resize(n);
+        if (hipMemcpy(rec.data(), e->P.sc_rec + off, n * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(dist.data(), e->P.dist + off, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(tags.data(), e->P.gtag + off, n * sizeof(uint16_t), hipMemcpyDeviceToHost) != hipSuccess)
             return;
@@ -1151,7 +1151,7 @@ void restore_table_after_overrun(cc_engine* e, int stream, const StreamState& st
             for (int row = R - 1; row >= 0; row--)
             {
                 const bool has = tags[o + (size_t) row] == tag && !std::isnan(dist[o + (size_t) row]);
-                const float cur = has ? incl[o + (size_t) row] : std::nanf("");
+                const float cur = has ? rec[o + (size_t) row].w : std::nanf("");
                 const float diff = cur - below;
                 if (!std::isnan(diff) && !found[(size_t) row])
                 {

@@ -301,7 +301,7 @@ constexpr int IP_MAXF = 4608; // firings of a batch k_insert_par can take (LDS t
 // Pointers of one stream (planes offset to the stream's first cell / column / pool slot).
 struct SP
 {
-    float *dist, *incl, *tabc;
+    float *dist, *tabc;
     float* incaz;
     uint16_t* gtag;
     uint32_t* src;
@@ -351,7 +351,6 @@ __device__ __forceinline__ SP stream_ptrs(const Planes& P, const Geometry& g, in
     const size_t lo = (size_t) s * (size_t) g.ring_cols;
     const size_t to = (size_t) s * (size_t) g.tree_capacity;
     p.dist = P.dist + co;
-    p.incl = P.incl + co;
     p.incaz = P.incaz + co;
     p.gtag = P.gtag + co;
     p.src = P.src + co;

@@ -257,7 +257,6 @@ __device__ __forceinline__ void insert2_body(const Geometry& g, const cc_config&
                 {
                     const size_t ci = (size_t) clc * R + row;
                     p.dist[ci] = __builtin_nanf("");
-                    p.incl[ci] = __builtin_nanf("");
                     p.gtag[ci] = CELL_CLEARED;
                 }
             }
@@ -453,7 +452,6 @@ __device__ __forceinline__ void insert2_body(const Geometry& g, const cc_config&
                         p.inten[ci] = (uint8_t) r_t[so];
                         p.src[ci] = (uint32_t) (seq0 + (f - cursor0));
                         p.dist[ci] = d;
-                        p.incl[ci] = r_i[so];
                         p.incaz[ci] = pack_incaz(r_a[so], c0 >= NC); // (rotation of the return: prev_rot, the column's unless c0 == NC)
                         p.gtag[ci] = tag0;
                         w_dist[wcol + row] = d;
@@ -677,7 +675,6 @@ __device__ __forceinline__ void insert2_body(const Geometry& g, const cc_config&
                     p.sc_rec[ci] = make_float4(r_x[so], r_y[so], r_z[so], r_i[so]);
                     p.inten[ci] = (uint8_t) r_t[so];
                     p.src[ci] = (uint32_t) (seq0 + (f - cursor0));
-                    p.incl[ci] = r_i[so];
                     // rotation of the return = prev_rot + rot_off (cc.cpp:184-186) = that of its column gc = gcv (+ 1 if moved on), or one less
                     p.incaz[ci] = pack_incaz(r_a[so], cir[k] + (int) (gc - gcv[k]) >= NC);
                     p.gtag[ci] = cell_tag(pass);
@@ -842,8 +839,8 @@ __global__ __launch_bounds__(128) void k_insert2(Geometry g, cc_config cfg, Plan
 
 // ---- pieces shared by k_insert_par and k_insert_par_fin ---------------------------------------------------------------------------
 // take back what firings behind the first offending one have written: every cell of the columns (rel_from .. rel_to past prev_rear0) returns
-// to the cleared state (clearColumns' three planes: all the serial kernel looks at). Whole columns: with the fused segmentation cells without
-// a return carry the ring-pass tag as well.
+// to the cleared state (clearColumns' two planes, dist = NaN and gtag = CELL_CLEARED: all the serial kernel looks at; the records stay and are
+// never seen, cc_device.h: Planes::dist). Whole columns: with the fused segmentation cells without a return carry the ring-pass tag as well.
 template<int RPL>
 __device__ __forceinline__ void par_take_back(const SP& p, const int R, const int RC, const int lc0, const int rel_from, const int rel_to, const int wave,
                                               const int nwaves, const int lane)
@@ -859,7 +856,6 @@ __device__ __forceinline__ void par_take_back(const SP& p, const int R, const in
             {
                 const size_t ci = (size_t) lc * R + row;
                 p.dist[ci] = __builtin_nanf("");
-                p.incl[ci] = __builtin_nanf("");
                 p.gtag[ci] = CELL_CLEARED;
             }
         }
@@ -1248,7 +1244,6 @@ __global__ __launch_bounds__(64 * W, CC_IP_MIN_WAVES_PER_SIMD) void k_insert_par
                 {
                     const size_t ci = (size_t) clc * R + row;
                     p.dist[ci] = __builtin_nanf("");
-                    p.incl[ci] = __builtin_nanf("");
                     p.gtag[ci] = CELL_CLEARED;
                 }
             }
@@ -1670,7 +1665,6 @@ __global__ __launch_bounds__(64 * W, CC_IP_MIN_WAVES_PER_SIMD) void k_insert_par
                 at32(p.inten, ci) = cint[k];
                 at32(p.src, ci) = (uint32_t) (seq0 + f);
                 at32(p.dist, ci) = q[k].dist;
-                at32(p.incl, ci) = q[k].incl;
                 at32(p.incaz, ci) = q[k].incaz; // (c0 < num_columns and nothing moves on: the return's rotation is its column's)
             }
         }
@@ -1889,7 +1883,6 @@ __global__ __launch_bounds__(64 * IM_WAVES) void k_insert_multi(Geometry g, cc_c
                 {
                     const size_t ci = (size_t) clc * R + row;
                     p.dist[ci] = __builtin_nanf("");
-                    p.incl[ci] = __builtin_nanf("");
                     p.gtag[ci] = CELL_CLEARED;
                 }
             }
@@ -2232,7 +2225,6 @@ __global__ __launch_bounds__(64 * IM_WAVES) void k_insert_multi(Geometry g, cc_c
                     const int lc = (int) ((unsigned) (lc0 + crel) - lcq * (unsigned) RC);
                     const unsigned ci = (unsigned) lc * (unsigned) R + (unsigned) row;
                     at32(p.sc_rec, ci) = make_float4(q[k].x, q[k].y, q[k].z, q[k].incl);
-                    at32(p.incl, ci) = q[k].incl;
 #if !CC_IM_STAGE
                     at32(p.inten, ci) = cint[k];
                     at32(p.src, ci) = (uint32_t) (seq0 + (f - cursor0));

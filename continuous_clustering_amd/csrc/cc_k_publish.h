@@ -49,7 +49,9 @@ __device__ __forceinline__ void view_column(const Geometry& g, const SP& p, cons
         o.y[oi] = rec.y;
         o.z[oi] = rec.z;
         o.dist[oi] = has_point ? p.dist[ci] : nanf_;
-        o.incl[oi] = (has_point || segmented) ? p.incl[ci] : nanf_;
+        // (the published inclination, cc_device.h: Planes::dist — every cell of a segmented column carries a record of this pass, whose .w is the raw
+        // or the supplemented inclination; elsewhere a record without a point is the previous tenant's)
+        o.incl[oi] = has_point ? rec.w : (segmented ? p.sc_rec[ci].w : nanf_);
         // (a segmented cell without a return sits in the middle of its column, cc.cpp:371-372)
         o.caz[oi] = has_point ? cell_caz(cb, p.incaz[ci]) : (segmented ? empty_cell_caz(gc, g.az_width) : __builtin_nan(""));
         o.gcol[oi] = segmented ? gc : (has_point ? gc : -1);

@@ -2,7 +2,7 @@
 // (cc_engine_reset_streams).
 // (part of cc_kernels.h: included there, in order, inside namespace cck)
 //
-// What the engine's whole reset does with ten hipMemsetAsync over whole planes and one copy of every stream's StreamState, this kernel does for the
+// What the engine's whole reset does with nine hipMemsetAsync over whole planes and one copy of every stream's StreamState, this kernel does for the
 // listed streams' slices only: the same planes, the same fill bytes, the same StreamState (built on the host by the function the whole reset
 // uses), and the streams' hand-over cursors. Every other stream is live: the slice of stream s of a plane is the bytes [s * bytes, (s + 1) * bytes)
 // and nothing outside it is written. A slice does not start on 16 bytes in general (1- and 2-byte planes, odd cell counts): fill_slice writes
@@ -11,7 +11,7 @@
 // listed twice is written twice with the same values.
 #pragma once
 
-constexpr int RESET_PLANES = 10;   // dist, incl, gtag, id, ground, debug, ignored, root, tab_acc, sl_ctl (cc_engine.hip: reset_state)
+constexpr int RESET_PLANES = 9;    // dist, gtag, id, ground, debug, ignored, root, tab_acc, sl_ctl (cc_engine.hip: reset_state)
 constexpr int RESET_THREADS = 256;
 constexpr unsigned long long RESET_CHUNK_BYTES = 16384; // of the longest slice per block, while the launch stays below RESET_MAX_BLOCKS blocks
 constexpr int RESET_MAX_BLOCKS = 2048;

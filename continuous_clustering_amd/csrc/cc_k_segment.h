@@ -81,48 +81,94 @@ __global__ __launch_bounds__(64 * TABLE_WAVES) void k_table(Geometry g, Planes P
     const SP p = stream_ptrs(P, g, s);
     const int R = g.num_rows, RC = g.ring_cols;
     const int ntiles = (int) ((seg_end - seg_begin + 63) >> 6);
-    constexpr int U = 16;
+    // the value the row below / above holds (the next / previous lane; across the two registers of a 128-row sensor behind lane 63 / in front of lane 0)
+    auto below_i = [&](const int (&v)[RPL], const int k) -> int
+    {
+        const int nxt0 = __shfl(v[k + 1 < RPL ? k + 1 : k], 0, 64), dn = __shfl_down(v[k], 1, 64);
+        return lane == 63 ? (k + 1 < RPL ? nxt0 : 0) : dn;
+    };
+    auto above_i = [&](const int (&v)[RPL], const int k) -> int
+    {
+        const int prv = __shfl(v[k > 0 ? k - 1 : k], 63, 64), up = __shfl_up(v[k], 1, 64);
+        return lane == 0 ? (k > 0 ? prv : 0) : up;
+    };
+    // A cell's raw inclination is its record's .w if the cell holds a return of this pass over the ring (cc_device.h: Planes::dist), and a row's
+    // step is valid where its cell and the cell below both have one (the bottom row: its own, cc.cpp:309). Which cells do is in dist and gtag (6
+    // bytes a cell); the 16-byte records are read only where a step can come from. The tile is walked from its LAST column backwards, U columns at a
+    // time, until every row has its last valid step: on a dense scene that is the first round, and a row that never has a return costs no record.
+    constexpr int U = 8;
     for (int t = wave; t < ntiles; t += TABLE_WAVES)
     {
         const long long c_lo = seg_begin + 64ll * t, c_hi = (c_lo + 64 < seg_end ? c_lo + 64 : seg_end);
-        float last[RPL]; // NaN = no valid step in this tile so far
+        float last[RPL]; // NaN = no valid step in this tile
+        int found[RPL];
 #pragma unroll
         for (int k = 0; k < RPL; k++)
-            last[k] = __builtin_nanf("");
-        int lc = (int) (c_lo % RC);
-        for (long long c0 = c_lo; c0 < c_hi; c0 += U)
         {
-            float cur[U][RPL], below[U][RPL];
+            last[k] = __builtin_nanf("");
+            found[k] = k * 64 + lane >= R ? 1 : 0;
+        }
+        for (long long c1 = c_hi; c1 > c_lo; c1 -= U) // columns [c1 - U, c1) of the tile, the highest first (u = 0)
+        {
+            bool through = true;
+#pragma unroll
+            for (int k = 0; k < RPL; k++)
+                through &= found[k] != 0;
+            if (__all(through))
+                break;
+            const int lc1 = (int) ((c1 - 1) % RC);
+            const long long pass1 = (c1 - 1) / RC; // pass over the ring (cell_tag)
+            int has[U][RPL];
 #pragma unroll
             for (int u = 0; u < U; u++)
             {
+                const bool in_tile = c1 - 1 - u >= c_lo;
+                const int lcu = lc1 - u < 0 ? lc1 - u + RC : lc1 - u;
+                const uint16_t tag = cell_tag(lc1 - u < 0 ? pass1 - 1 : pass1);
 #pragma unroll
                 for (int k = 0; k < RPL; k++)
                 {
                     const int row = k * 64 + lane;
-                    cur[u][k] = below[u][k] = 0.f;
-                    if (row < R && c0 + u < c_hi)
+                    has[u][k] = 0;
+                    if (row < R && in_tile)
                     {
-                        const size_t ci = (size_t) lc * R + row;
-                        cur[u][k] = p.incl[ci];
-                        below[u][k] = row + 1 < R ? p.incl[ci + 1] : 0.f;
+                        const size_t ci = (size_t) lcu * R + row;
+                        const float d = p.dist[ci];
+                        has[u][k] = (p.gtag[ci] == tag && !(d != d)) ? 1 : 0;
                     }
                 }
-                lc = lc + 1 == RC ? 0 : lc + 1;
             }
+            float w[U][RPL];
+            int cand[U][RPL];
 #pragma unroll
             for (int u = 0; u < U; u++)
             {
-                if (c0 + u >= c_hi)
-                    break;
+                const int lcu = lc1 - u < 0 ? lc1 - u + RC : lc1 - u;
 #pragma unroll
                 for (int k = 0; k < RPL; k++)
                 {
-                    const float diff = cur[u][k] - below[u][k];
-                    if (!(diff != diff))
-                        last[k] = diff;
+                    const int row = k * 64 + lane;
+                    const int has_below = below_i(has[u], k), has_above = above_i(has[u], k), found_above = above_i(found, k);
+                    cand[u][k] = (has[u][k] && !found[k] && (row + 1 < R ? has_below : 1)) ? 1 : 0;
+                    w[u][k] = 0.f;
+                    if (cand[u][k] || (has[u][k] && has_above && !found_above)) // (this row's own step, or the step of the row above)
+                        w[u][k] = p.sc_rec[(size_t) lcu * R + row].w;
                 }
             }
+#pragma unroll
+            for (int u = 0; u < U; u++)
+#pragma unroll
+                for (int k = 0; k < RPL; k++)
+                {
+                    const int row = k * 64 + lane;
+                    const float nxt0 = __shfl(w[u][k + 1 < RPL ? k + 1 : k], 0, 64), dn = __shfl_down(w[u][k], 1, 64);
+                    const float diff = w[u][k] - (row + 1 < R ? (lane == 63 ? nxt0 : dn) : 0.f);
+                    if (cand[u][k] && !found[k] && !(diff != diff))
+                    {
+                        last[k] = diff;
+                        found[k] = 1;
+                    }
+                }
         }
 #pragma unroll
         for (int k = 0; k < RPL; k++)
@@ -480,7 +526,6 @@ __global__ __launch_bounds__(64, CC_SEGSCAN_MIN_WAVES_PER_SIMD) void k_seg_scan(
         const float* gw = p.sg_w + (size_t) lcl * R;
         const unsigned char* gf = p.sg_flags + (size_t) lcl * R;
         float4* g_rec = p.sc_rec + (size_t) lcl * R; // (cells without a return: .w = the supplemented inclination, what the window scan reads)
-        float* g_incl = p.incl + (size_t) lcl * R;
         const float* tab_in = p.tabc + (size_t) blockIdx.y * R; // the table in front of this tile (wave-uniform: scalar loads)
         unsigned char* oo = l_out + lane * PB;
         const float height_sensor_to_ground = -(float) st->robot_from_sensor[11] + cfg.height_ref_to_ground_;
@@ -587,10 +632,7 @@ __global__ __launch_bounds__(64, CC_SEGSCAN_MIN_WAVES_PER_SIMD) void k_seg_scan(
             const bool is_nan = (f & SG_NAN) != 0;
             const float supp = (supplement & (row < R - 1)) ? (below_nan ? supp_below : wv) + tab : __builtin_nanf("");
             if (is_nan & active)
-            {
                 g_rec[row].w = supp; // (x, y, z stay: a return with a NaN range is published with them, cc_device.h: NAN_RANGE_BITS)
-                g_incl[row] = supp;
-            }
             supp_below = is_nan ? supp : supp_below;
             below_nan = is_nan;
             // cc.cpp:597-603 with the table entry of an earlier column: atan2f(max_distance, distance) < tab. Two rigorous bounds first
@@ -1144,10 +1186,7 @@ __device__ __forceinline__ void seg_small_body(const Geometry& g, const cc_confi
             if (empty_cell)
                 p.gtag[ci] = tag;
             if (is_nan)
-            {
                 p.sc_rec[ci].w = sincl; // (x, y, z stay: a return with a NaN range is published with them, cc_device.h: NAN_RANGE_BITS)
-                p.incl[ci] = sincl;
-            }
         }
         int kpos = 0x7fffffff, kneg = 0x7fffffff;
         if (inrow && !is_nan)
