@@ -11,7 +11,7 @@ LIB = os.path.join(HERE, "libcc_hip.so")
 SOURCES = ["cc_engine.hip", "cc_eval.hip", "cc_kitti.hip", "cc_gt_labels.hip", "cc_ouster.hip", "cc_velodyne.hip", "cc_points.hip", "cc_poses.hip", "cc_stamps.hip"]
 DEPS = ["cc_engine.hip", "cc_eval.hip", "cc_kitti.hip", "cc_gt_labels.hip", "cc_ouster.hip", "cc_velodyne.hip", "cc_points.hip", "cc_poses.hip", "cc_stamps.hip", "cc_pose_math.h", "cc_stamp_math.h", os.path.join("..", "..", "include", "cc_poses.h"), os.path.join("..", "..", "include", "cc_stamps.h"), os.path.join("..", "..", "include", "cc_kitti.h"),
         os.path.join("..", "..", "include", "cc_velodyne.h"), os.path.join("..", "..", "include", "cc_points.h"),
-        os.path.join("..", "..", "include", "cc_ouster.h"), os.path.join("..", "..", "include", "cc_ouster_profiles.h"), "cc_assoc_shared.h", "cc_assoc3.h", "cc_assocb.h", "cc_kernels.h", "cc_buffers.h", "cc_launch.h", "cc_options.h", "cc_k_base.h", "cc_k_segcells.h", "cc_k_insert.h", "cc_k_segment.h", "cc_k_assoc_global.h", "cc_k_scan.h", "cc_k_assoc_lds.h", "cc_k_publish.h", "cc_k_take.h", "cc_k_take_clusters.h", "cc_k_reset.h", "cc_k_replay_eval.h", "cc_replay_eval.h", "cc_eval_shared.h", "cc_device.h", "cc_math.h", os.path.join("..", "..", "include", "cc_hip.h")]
+        os.path.join("..", "..", "include", "cc_ouster.h"), os.path.join("..", "..", "include", "cc_ouster_profiles.h"), "cc_assoc_shared.h", "cc_assoc3.h", "cc_assocb.h", "cc_kernels.h", "cc_buffers.h", "cc_launch.h", "cc_options.h", "cc_k_base.h", "cc_k_segcells.h", "cc_k_insert.h", "cc_k_segment.h", "cc_k_assoc_global.h", "cc_k_scan.h", "cc_k_assoc_lds.h", "cc_k_held.h", "cc_k_publish.h", "cc_k_take.h", "cc_k_take_clusters.h", "cc_k_reset.h", "cc_k_replay_eval.h", "cc_take.h", "cc_replay_eval.h", "cc_eval_shared.h", "cc_device.h", "cc_math.h", os.path.join("..", "..", "include", "cc_hip.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-variable", "-Wno-bitwise-instead-of-logical", "-ldl"]
 

@@ -2429,281 +2429,6 @@ int cc_engine_gather_cluster_points(cc_engine* e, int stream, int64_t n, const u
     return CC_OK;
 }
 
-// ---- hand-over of the published points in device memory (cc_k_take.h) ----------------------------------------------
-// the cursors, the plan and the control block, by the first take (the device blocks again after a change of shape: free_all)
-static int ensure_take(cc_engine* e)
-{
-    const size_t S = (size_t) e->g.num_streams;
-    int rc;
-    if (!e->h_take && (rc = alloc_pinned(e, &e->h_take, S * sizeof(cc_take_stream) + sizeof(cck::TakeCtl), PIN_ENGINE)))
-        return rc;
-    if (e->d_take_cursor)
-        return CC_OK;
-    // (the members are set once all three blocks are there: a call that fails half way leaves nothing behind that a later call would take for complete)
-    long long* cur = nullptr;
-    cc_take_stream* plan = nullptr;
-    cck::TakeCtl* ctl = nullptr;
-    if ((rc = alloc_plane(e, &cur, 2 * S)) || (rc = alloc_plane(e, &plan, S)) || (rc = alloc_plane(e, &ctl, 1)))
-        return rc;
-    // (in stream order and waited for: a hipMemset on the null stream is not ordered against the engine's streams, and recycled device memory is not zero)
-    CC_HIP_CHECK(e, hipMemsetAsync(cur, 0, 2 * S * sizeof(long long), query_stream(e)));
-    CC_HIP_CHECK(e, hipStreamSynchronize(query_stream(e)));
-    e->d_take_plan = plan;
-    e->d_take_ctl = ctl;
-    e->d_take_cursor = cur;
-    return CC_OK;
-}
-
-// what the three take functions share: arguments, the resident kernel, the batches in flight, the buffers
-static int take_enter(cc_engine* e, const char* who, int stage)
-{
-    if (!e)
-        return CC_ERR_INVALID_ARGUMENT;
-    if (stage != CC_TAKE_CLUSTERED && stage != CC_TAKE_SEGMENTED)
-    {
-        e->error = std::string(who) + ": stage must be CC_TAKE_CLUSTERED or CC_TAKE_SEGMENTED";
-        return CC_ERR_INVALID_ARGUMENT;
-    }
-    if (e->resident_opt)
-    {
-        e->error = std::string(who) + ": not available while the option \"resident\" is on (the resident kernel owns the stream's state); set it to 0 first";
-        return CC_ERR_INVALID_ARGUMENT;
-    }
-    (void) hipSetDevice(e->device);
-    int rc = finish_batch(e);
-    if (rc)
-        return rc;
-    return ensure_take(e);
-}
-
-int cc_engine_take_points(cc_engine* e, int stage, int select, cc_take_point* d_records, int64_t capacity, cc_take_stream* d_table,
-                          cc_take_stream* h_table, int64_t* n_records)
-{
-    if (!e)
-        return CC_ERR_INVALID_ARGUMENT;
-    const char* bad = nullptr;
-    if (select != CC_TAKE_ALL_RETURNS && select != CC_TAKE_NOT_GROUND && select != CC_TAKE_WITH_ID)
-        bad = "select must be CC_TAKE_ALL_RETURNS, CC_TAKE_NOT_GROUND or CC_TAKE_WITH_ID";
-    else if (select == CC_TAKE_WITH_ID && stage == CC_TAKE_SEGMENTED)
-        bad = "CC_TAKE_WITH_ID needs the CLUSTERED stage (segmented columns have no final ids)";
-    else if (capacity < 0 || (!d_records && capacity != 0))
-        bad = "capacity must be >= 0, and 0 without a record array (the size query)";
-    else if (((uintptr_t) d_records & 15u) != 0)
-        bad = "d_records must be 16-byte aligned";
-    else if (!h_table || !n_records)
-        bad = "h_table and n_records must not be NULL";
-    if (bad)
-    {
-        e->error = std::string("cc_engine_take_points: ") + bad;
-        return CC_ERR_INVALID_ARGUMENT;
-    }
-    int rc = take_enter(e, "cc_engine_take_points", stage);
-    if (rc)
-        return rc;
-    const int S = e->g.num_streams;
-    hipStream_t q = query_stream(e);
-    cc_take_stream* h_plan = (cc_take_stream*) e->h_take;
-    cck::TakeCtl* h_ctl = (cck::TakeCtl*) (e->h_take + (size_t) S * sizeof(cc_take_stream));
-    hipLaunchKernelGGL(cck::k_take_plan, dim3((unsigned) ((S + 63) / 64)), dim3(64), 0, q, e->g, e->d_states, e->d_take_cursor, stage, e->d_take_plan, h_plan);
-    CC_HIP_CHECK(e, hipGetLastError());
-    CC_HIP_CHECK(e, hipStreamSynchronize(q));
-    // the grids follow the longest range of the plan, not the ring
-    int64_t longest = 0;
-    for (int s = 0; s < S; s++)
-        longest = std::max<int64_t>(longest, h_plan[s].col_to - h_plan[s].col_from);
-    if (longest > e->g.ring_cols)
-    {
-        e->error = "cc_engine_take_points: a range longer than the ring";
-        return CC_ERR_BOOKKEEPING;
-    }
-    const int stride = (int) std::max<int64_t>(longest, 1);
-    // (twice what is needed, at most a ring per stream: ranges that creep up from take to take must not allocate a new block each time)
-    const size_t counts_need = (size_t) S * (size_t) stride;
-    if ((rc = grow_scratch(e, &e->d_take_counts, &e->take_counts_cap, counts_need, std::min(2 * counts_need, (size_t) S * (size_t) e->g.ring_cols))))
-        return rc;
-    if (longest > 0)
-        hipLaunchKernelGGL(cck::k_take_count, dim3((unsigned) longest, (unsigned) S), dim3(64), 0, q, e->g, e->P, e->d_take_plan, select, e->d_take_counts, stride);
-    hipLaunchKernelGGL(cck::k_take_scan, dim3((unsigned) S), dim3(cck::TAKE_SCAN_THREADS), 0, q, e->d_take_plan, e->d_take_counts, stride);
-    hipLaunchKernelGGL(cck::k_take_scan_streams, dim3(1), dim3(cck::TAKE_SCAN_THREADS), 0, q, S, e->d_take_plan, (long long) capacity, d_records ? 1 : 0,
-                       e->d_take_ctl, d_table, h_plan, h_ctl);
-    if (d_records) // (the kernel looks at the verdict itself: nothing is written and no cursor moves unless every record fits)
-        hipLaunchKernelGGL(cck::k_take_write, dim3((unsigned) stride, (unsigned) S), dim3(64), 0, q, e->g, e->P, e->d_take_plan, e->d_take_ctl, stage, select,
-                           e->d_take_counts, stride, d_records, e->d_take_cursor);
-    CC_HIP_CHECK(e, hipGetLastError());
-    CC_HIP_CHECK(e, hipStreamSynchronize(q));
-    memcpy(h_table, h_plan, (size_t) S * sizeof(cc_take_stream));
-    *n_records = h_ctl->total;
-    if (h_ctl->total > capacity)
-    {
-        e->error = "cc_engine_take_points: " + std::to_string(h_ctl->total) + " records do not fit a capacity of " + std::to_string(capacity) +
-                   " (nothing was written, no cursor moved)";
-        return CC_ERR_CAPACITY;
-    }
-    return CC_OK;
-}
-
-int cc_engine_take_cursor(cc_engine* e, int stage, int stream, int64_t* cursor, int64_t* readable_from)
-{
-    if (!e || stream < 0 || stream >= e->g.num_streams)
-        return CC_ERR_INVALID_ARGUMENT;
-    int rc = take_enter(e, "cc_engine_take_cursor", stage);
-    if (rc)
-        return rc;
-    long long cur = 0;
-    StreamState st;
-    CC_HIP_CHECK(e, hipMemcpy(&cur, e->d_take_cursor + (size_t) stage * e->g.num_streams + stream, sizeof(cur), hipMemcpyDeviceToHost));
-    CC_HIP_CHECK(e, hipMemcpy(&st, e->d_states + stream, sizeof(st), hipMemcpyDeviceToHost));
-    if (cursor)
-        *cursor = cur;
-    if (readable_from)
-        *readable_from = std::max<int64_t>(0, std::max(st.clear_done, st.first_column));
-    return CC_OK;
-}
-
-int cc_engine_take_seek(cc_engine* e, int stage, int stream, int64_t column)
-{
-    if (!e || stream < -1 || stream >= e->g.num_streams || column < 0)
-        return CC_ERR_INVALID_ARGUMENT;
-    int rc = take_enter(e, "cc_engine_take_seek", stage);
-    if (rc)
-        return rc;
-    const int first = stream < 0 ? 0 : stream, count = stream < 0 ? e->g.num_streams : 1;
-    const std::vector<long long> v((size_t) count, (long long) column);
-    CC_HIP_CHECK(e, hipMemcpy(e->d_take_cursor + (size_t) stage * e->g.num_streams + first, v.data(), (size_t) count * sizeof(long long), hipMemcpyHostToDevice));
-    return CC_OK;
-}
-
-// ---- hand-over of the finished clusters in device memory (cc_k_take_clusters.h) -------------------------------------
-// the cursor pairs, the plan, the table and the control block, by the first take (the device blocks again after a change of shape: free_all)
-static int ensure_take_clusters(cc_engine* e)
-{
-    const size_t S = (size_t) e->g.num_streams;
-    int rc;
-    if (!e->h_tc && (rc = alloc_pinned(e, &e->h_tc, S * (sizeof(cck::TcPlan) + sizeof(cc_take_cluster_stream)) + sizeof(cck::TcCtl), PIN_ENGINE)))
-        return rc;
-    if (e->d_tc_cursor)
-        return CC_OK;
-    // (the members are set once all blocks are there, as in ensure_take)
-    long long* cur = nullptr;
-    cck::TcPlan* plan = nullptr;
-    cc_take_cluster_stream* table = nullptr;
-    cck::TcCtl* ctl = nullptr;
-    if ((rc = alloc_plane(e, &cur, 2 * S)) || (rc = alloc_plane(e, &plan, S)) || (rc = alloc_plane(e, &table, S)) || (rc = alloc_plane(e, &ctl, 1)))
-        return rc;
-    CC_HIP_CHECK(e, hipMemsetAsync(cur, 0, 2 * S * sizeof(long long), query_stream(e)));
-    CC_HIP_CHECK(e, hipStreamSynchronize(query_stream(e)));
-    e->d_tc_plan = plan;
-    e->d_tc_table = table;
-    e->d_tc_ctl = ctl;
-    e->d_tc_cursor = cur;
-    return CC_OK;
-}
-
-int cc_engine_take_clusters(cc_engine* e, uint32_t min_points, int flags, cc_take_cluster* d_clusters, int64_t cluster_capacity, cc_take_point* d_records,
-                            int64_t record_capacity, cc_take_cluster_stream* d_table, cc_take_cluster_stream* h_table, int64_t* n_clusters,
-                            int64_t* n_records)
-{
-    if (!e)
-        return CC_ERR_INVALID_ARGUMENT;
-    const bool with_points = flags == CC_TAKE_CLUSTERS_WITH_POINTS;
-    const char* bad = nullptr;
-    if (flags != CC_TAKE_CLUSTERS_WITH_POINTS && flags != CC_TAKE_CLUSTERS_DESCRIPTORS_ONLY)
-        bad = "flags must be CC_TAKE_CLUSTERS_WITH_POINTS or CC_TAKE_CLUSTERS_DESCRIPTORS_ONLY";
-    else if (cluster_capacity < 0 || (!d_clusters && cluster_capacity != 0))
-        bad = "cluster_capacity must be >= 0, and 0 without a descriptor array (the size query)";
-    else if (record_capacity < 0 || (!d_records && record_capacity != 0))
-        bad = "record_capacity must be >= 0, and 0 without a record array";
-    else if (d_clusters && with_points && !d_records)
-        bad = "d_records must not be NULL unless CC_TAKE_CLUSTERS_DESCRIPTORS_ONLY is set";
-    else if (((uintptr_t) d_clusters & 15u) != 0 || ((uintptr_t) d_records & 15u) != 0)
-        bad = "d_clusters and d_records must be 16-byte aligned";
-    else if (((uintptr_t) d_table & 7u) != 0)
-        bad = "d_table must be 8-byte aligned";
-    else if (!h_table || !n_clusters || !n_records)
-        bad = "h_table, n_clusters and n_records must not be NULL";
-    if (bad)
-    {
-        e->error = std::string("cc_engine_take_clusters: ") + bad;
-        return CC_ERR_INVALID_ARGUMENT;
-    }
-    int rc = take_enter(e, "cc_engine_take_clusters", CC_TAKE_CLUSTERED);
-    if (rc || (rc = ensure_take_clusters(e)))
-        return rc;
-    const int S = e->g.num_streams;
-    hipStream_t q = query_stream(e);
-    cck::TcPlan* h_plan = (cck::TcPlan*) e->h_tc;
-    cc_take_cluster_stream* h_tab = (cc_take_cluster_stream*) (e->h_tc + (size_t) S * sizeof(cck::TcPlan));
-    cck::TcCtl* h_ctl = (cck::TcCtl*) (e->h_tc + (size_t) S * (sizeof(cck::TcPlan) + sizeof(cc_take_cluster_stream)));
-    hipLaunchKernelGGL(cck::k_tc_plan, dim3(1), dim3(cck::TAKE_SCAN_THREADS), 0, q, e->g, e->d_states, e->d_tc_cursor, e->d_tc_plan, e->d_tc_table, h_plan, h_ctl);
-    CC_HIP_CHECK(e, hipGetLastError());
-    CC_HIP_CHECK(e, hipStreamSynchronize(q));
-    // the grids follow the plan: the longest column range, the longest id range, the ids of all streams
-    int64_t longest_cols = 0, longest_ids = 0;
-    for (int s = 0; s < S; s++)
-    {
-        longest_cols = std::max<int64_t>(longest_cols, h_plan[s].col_to - h_plan[s].col_from);
-        longest_ids = std::max<int64_t>(longest_ids, h_plan[s].n_ids);
-    }
-    const int64_t total_ids = h_ctl->total_ids;
-    if (longest_cols > e->g.ring_cols || total_ids < 0 || total_ids + S > 0x7fffffffll)
-    {
-        e->error = "cc_engine_take_clusters: a range longer than the ring, or more ids than a grid has blocks";
-        return CC_ERR_BOOKKEEPING;
-    }
-    // (twice what is needed: id counts that creep up from take to take must not allocate a new block each time)
-    const size_t slots_need = (size_t) std::max<int64_t>(total_ids, 1);
-    if ((rc = grow_scratch(e, &e->d_tc_slots, &e->tc_slots_cap, slots_need, 2 * slots_need)))
-        return rc;
-    if (total_ids > 0)
-    {
-        hipLaunchKernelGGL(cck::k_tc_clear, dim3((unsigned) ((longest_ids + cck::TAKE_SCAN_THREADS - 1) / cck::TAKE_SCAN_THREADS), (unsigned) S),
-                           dim3(cck::TAKE_SCAN_THREADS), 0, q, e->d_tc_plan, e->d_tc_slots, (long long) total_ids);
-        if (longest_cols > 0)
-            hipLaunchKernelGGL(cck::k_tc_mark, dim3((unsigned) longest_cols, (unsigned) S), dim3(64), 0, q, e->g, e->P, e->d_tc_plan, e->d_tc_table,
-                               e->d_tc_slots, (long long) total_ids);
-    }
-    hipLaunchKernelGGL(cck::k_tc_scan, dim3((unsigned) S), dim3(cck::TAKE_SCAN_THREADS), 0, q, e->d_tc_plan, e->d_tc_table, e->d_tc_slots, (long long) total_ids,
-                       (unsigned) min_points);
-    hipLaunchKernelGGL(cck::k_tc_scan_streams, dim3(1), dim3(cck::TAKE_SCAN_THREADS), 0, q, S, e->d_tc_table, (long long) cluster_capacity,
-                       (long long) record_capacity, d_clusters ? 1 : 0, with_points ? 1 : 0, (long long) total_ids, e->d_tc_ctl, d_table, h_tab, h_ctl);
-    if (d_clusters) // (the kernel looks at the verdict itself: nothing is written and no cursor moves unless everything fits)
-        hipLaunchKernelGGL(cck::k_tc_write, dim3((unsigned) (S + total_ids)), dim3(64), 0, q, e->g, e->P, e->d_tc_plan, e->d_tc_table, e->d_tc_ctl, e->d_tc_slots,
-                           (long long) total_ids, d_clusters, with_points ? d_records : nullptr, e->d_tc_cursor);
-    CC_HIP_CHECK(e, hipGetLastError());
-    CC_HIP_CHECK(e, hipStreamSynchronize(q));
-    memcpy(h_table, h_tab, (size_t) S * sizeof(cc_take_cluster_stream));
-    *n_clusters = h_ctl->clusters;
-    *n_records = h_ctl->records;
-    if (h_ctl->clusters > cluster_capacity || (with_points && h_ctl->records > record_capacity))
-    {
-        e->error = "cc_engine_take_clusters: " + std::to_string(h_ctl->clusters) + " clusters with " + std::to_string(h_ctl->records) +
-                   " records do not fit capacities of " + std::to_string(cluster_capacity) + " and " + std::to_string(record_capacity) +
-                   " (nothing was written, no cursor moved)";
-        return CC_ERR_CAPACITY;
-    }
-    return CC_OK;
-}
-
-int cc_engine_take_clusters_cursor(cc_engine* e, int stream, int64_t* next_id, int64_t* floor_column, int64_t* readable_from)
-{
-    if (!e || stream < 0 || stream >= e->g.num_streams)
-        return CC_ERR_INVALID_ARGUMENT;
-    int rc = take_enter(e, "cc_engine_take_clusters_cursor", CC_TAKE_CLUSTERED);
-    if (rc || (rc = ensure_take_clusters(e)))
-        return rc;
-    long long cur[2] = {0, 0};
-    StreamState st;
-    CC_HIP_CHECK(e, hipMemcpy(cur, e->d_tc_cursor + 2 * (size_t) stream, sizeof(cur), hipMemcpyDeviceToHost));
-    CC_HIP_CHECK(e, hipMemcpy(&st, e->d_states + stream, sizeof(st), hipMemcpyDeviceToHost));
-    if (next_id)
-        *next_id = cur[0] + 1;
-    if (floor_column)
-        *floor_column = std::max<int64_t>(cur[1], std::max<int64_t>(0, st.first_column));
-    if (readable_from)
-        *readable_from = std::max<int64_t>(0, std::max(st.clear_done, st.first_column));
-    return CC_OK;
-}
-
 // The first request for the id plane: from here on every path publishes ids per batch (Geometry::publish_ids), and the plane is brought up to
 // date once for what was published without it. What was held back goes through and every chain is waited for, as in the take functions; the
 // resident kernel and the captured small-call graphs bake the geometry in, so they go, as in cc_engine_set_option.
@@ -2832,70 +2557,6 @@ int cc_engine_totals(cc_engine* e, uint64_t* cells_published, uint64_t* clusters
     return CC_OK;
 }
 
-// ---- frame scatter of a replayed sequence (kitti_demo.cpp:173-224), include/cc_kitti.h ------------------------------------------------
-int cc_engine_scatter_info(cc_engine* e, int n, const int32_t* streams, const int64_t* from, const int64_t* to, const int32_t* d_original_index,
-                           int slots, int32_t* h_min_frame, int32_t* h_max_frame)
-{
-    if (!e || n < 0 || slots < 1 || (n > 0 && (!streams || !from || !to || !d_original_index || !h_min_frame || !h_max_frame)))
-        return CC_ERR_INVALID_ARGUMENT;
-    (void) hipSetDevice(e->device);
-    int rc = stop_resident(e);
-    if (rc)
-        return rc;
-    rc = finish_batch(e);
-    if (rc)
-        return rc;
-    size_t total = 0;
-    for (int i = 0; i < n; i++)
-    {
-        if (streams[i] < 0 || streams[i] >= e->g.num_streams || from[i] < 0 || to[i] - from[i] >= e->g.ring_cols)
-            return CC_ERR_INVALID_ARGUMENT; // (columns outside the stream's published ring window read as empty: the kernels check)
-        if (to[i] >= from[i])
-            total += (size_t) (to[i] - from[i] + 1);
-    }
-    if (total == 0)
-        return CC_OK;
-    if ((rc = ensure_gather(e, total * 8 + 64)))
-        return rc;
-    int* d_min = (int*) e->d_gather;
-    int* d_max = d_min + total;
-    size_t o = 0;
-    for (int i = 0; i < n; i++)
-        if (to[i] >= from[i])
-        {
-            const unsigned cols = (unsigned) (to[i] - from[i] + 1);
-            hipLaunchKernelGGL(cck::k_scatter_info, dim3(cols), dim3(64), 0, e->stream, e->g, e->P, (const StreamState*) e->d_states, streams[i], (long long) from[i], d_original_index,
-                               slots, d_min + o, d_max + o);
-            o += cols;
-        }
-    CC_HIP_CHECK(e, hipGetLastError());
-    CC_HIP_CHECK(e, hipMemcpyAsync(h_min_frame, d_min, total * 4, hipMemcpyDeviceToHost, e->stream));
-    CC_HIP_CHECK(e, hipMemcpyAsync(h_max_frame, d_max, total * 4, hipMemcpyDeviceToHost, e->stream));
-    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream));
-    return CC_OK;
-}
-
-int cc_engine_scatter_apply(cc_engine* e, int stream, int64_t from, int64_t to, const int32_t* d_original_index, int slots, uint8_t* d_is_ground,
-                            uint32_t* d_detection, int64_t max_points)
-{
-    if (!e || stream < 0 || stream >= e->g.num_streams || slots < 1 || !d_original_index || !d_is_ground || !d_detection || max_points < 1 ||
-        from < 0 || to - from >= e->g.ring_cols)
-        return CC_ERR_INVALID_ARGUMENT;
-    if (to < from)
-        return CC_OK;
-    (void) hipSetDevice(e->device);
-    int rc = stop_resident(e);
-    if (rc)
-        return rc;
-    rc = finish_batch(e);
-    if (rc)
-        return rc;
-    hipLaunchKernelGGL(cck::k_scatter_apply, dim3((unsigned) (to - from + 1)), dim3(64), 0, e->stream, e->g, e->P, (const StreamState*) e->d_states, stream, (long long) from,
-                       d_original_index, slots, d_is_ground, d_detection, (long long) max_points);
-    CC_HIP_CHECK(e, hipGetLastError());
-    return CC_OK; // (asynchronous on cc_engine_hip_stream(e): cc_eval_frame_device on the same stream, or cc_engine_sync, orders behind it)
-}
-
 int cc_engine_view_counters(cc_engine* e, uint64_t* served_from_mirror, uint64_t* served_by_kernel)
 {
     if (!e)
@@ -2980,4 +2641,5 @@ const char* cc_engine_last_error(cc_engine* e)
 
 } // extern "C"
 
-#include "cc_replay_eval.h" // the replay evaluator (cc_replay_eval_*, include/cc_kitti.h)
+#include "cc_take.h"        // the hand-overs in device memory (cc_engine_take_*, include/cc_hip.h)
+#include "cc_replay_eval.h" // the frame scatter and the replay evaluator (cc_engine_scatter_*, cc_replay_eval_*, include/cc_kitti.h)

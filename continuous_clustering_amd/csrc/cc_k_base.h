@@ -70,6 +70,42 @@ __device__ __forceinline__ int wave_min_i32(int v)
     CC_DPP_REDUCE(int, dpp_mov_i32, v, fill, CC_LESS)
     return __builtin_amdgcn_readlane(v, 63);
 }
+__device__ __forceinline__ float wave_min_f32(float v)
+{
+    int b = __float_as_int(v);
+    const int fill = 0x7f800000; // +inf
+#define CC_LESS_F32(a, b) (__int_as_float(a) < __int_as_float(b))
+    CC_DPP_REDUCE(int, dpp_mov_i32, b, fill, CC_LESS_F32)
+#undef CC_LESS_F32
+    return __int_as_float(__builtin_amdgcn_readlane(b, 63));
+}
+__device__ __forceinline__ float wave_max_f32(float v)
+{
+    int b = __float_as_int(v);
+    const int fill = (int) 0xff800000u; // -inf
+#define CC_GREATER_F32(a, b) (__int_as_float(a) > __int_as_float(b))
+    CC_DPP_REDUCE(int, dpp_mov_i32, b, fill, CC_GREATER_F32)
+#undef CC_GREATER_F32
+    return __int_as_float(__builtin_amdgcn_readlane(b, 63));
+}
+__device__ __forceinline__ unsigned wave_min_u32(unsigned v)
+{
+    int b = (int) v;
+    const int fill = -1;
+#define CC_LESS_U32(a, b) ((unsigned) (a) < (unsigned) (b))
+    CC_DPP_REDUCE(int, dpp_mov_i32, b, fill, CC_LESS_U32)
+#undef CC_LESS_U32
+    return (unsigned) __builtin_amdgcn_readlane(b, 63);
+}
+__device__ __forceinline__ unsigned wave_max_u32(unsigned v)
+{
+    int b = (int) v;
+    const int fill = 0;
+#define CC_GREATER_U32(a, b) ((unsigned) (a) > (unsigned) (b))
+    CC_DPP_REDUCE(int, dpp_mov_i32, b, fill, CC_GREATER_U32)
+#undef CC_GREATER_U32
+    return (unsigned) __builtin_amdgcn_readlane(b, 63);
+}
 __device__ __forceinline__ double wave_min_f64(double v)
 {
     // (no NaNs reach this: azimuths and finished_at values)

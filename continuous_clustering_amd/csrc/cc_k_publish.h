@@ -1,4 +1,4 @@
-// cc_k_publish.h — k_publish, k_small_tail, the frame scatter (k_scatter_info / k_scatter_apply), k_gather_clusters, k_view.
+// cc_k_publish.h — k_publish, k_publish_backlog, k_small_tail, k_small_all, k_resident, k_gather_clusters, k_view.
 // (part of cc_kernels.h: included there, in order, inside namespace cck)
 #pragma once
 
@@ -233,8 +233,7 @@ __global__ __launch_bounds__(64) void k_publish(Geometry g, Planes P, const Stre
 }
 
 // k_publish_backlog — the id plane brought up to date for every stream, once, when Geometry::publish_ids turns on (cc_engine_output_planes): the
-// ring slots of the published columns that are still held, [max(clear_done, first_column), first_unpublished), get what view_column shows for
-// them; every other slot keeps what it has. grid = (streams, PUBLISH_BLOCKS), block = 64, lanes = rows.
+// ring slots of the published columns that are still held, [held_from (cc_k_held.h), first_unpublished), get what view_column shows for them; every other slot keeps what it has. grid = (streams, PUBLISH_BLOCKS), block = 64, lanes = rows.
 // Reading t_cid[root] now instead of when the column was published gives the same value: a published cell's tree is finished, so neither its root
 // nor the root's id changes again. The root's column can fall below clear_done before the cell's column does, but clearing leaves t_cid alone and
 // the root's slot gets a new tenant only a full ring (10 rotations) later, when the cell's own column is long cleared — the same read view_column makes.
@@ -246,7 +245,7 @@ __global__ __launch_bounds__(64) void k_publish_backlog(Geometry g, Planes P, co
         return;
     const SP p = stream_ptrs(P, g, s);
     const int R = g.num_rows, RC = g.ring_cols;
-    long long lo = st->clear_done > st->first_column ? st->clear_done : st->first_column;
+    long long lo = held_from(st->first_column, st->clear_done, 0);
     // (view_column's `segmented`: inside the ring and below first_unfinished; first_unpublished never passes either)
     long long hi = st->first_unpublished < st->first_unfinished ? st->first_unpublished : st->first_unfinished;
     hi = hi < st->ring_end + 1 ? hi : st->ring_end + 1;
@@ -257,8 +256,7 @@ __global__ __launch_bounds__(64) void k_publish_backlog(Geometry g, Planes P, co
         for (int row = lane_id(); row < R; row += 64)
         {
             const int ci = lc * R + row;
-            const int r = p.root[ci];
-            p.id[ci] = (r >= 0 && r < (int) g.cells) ? p.t_cid[r] : 0u;
+            p.id[ci] = cell_cluster_id(p, ci, (int) g.cells);
         }
     }
 }
@@ -545,85 +543,6 @@ __global__ __launch_bounds__(AB_THREADS) void k_resident(Geometry g, cc_config c
                 __hip_atomic_store(&ctl->exited, (unsigned long long) reason, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             }
             return;
-        }
-    }
-}
-
-// =====================================================================================================
-// k_scatter_info / k_scatter_apply — the frame scatter of the reference's harness (addColumnAndEvaluateFrameIfCompleted,
-// kitti_demo.cpp:173-224) for a replayed KITTI sequence, on the device. A stream that is fed exactly num_columns pseudo-firings per frame
-// (kitti_demo.cpp:386-403) carries, per cell, the sequence number of the firing that filled it: frame = sequence / num_columns, range-image
-// column of the frame = sequence % num_columns, and the KITTI point of the cell is original_index[frame % slots][column][row]
-// (cc_kitti_frame::d_original_index of the frame's conversion). k_scatter_info gives the smallest / largest frame among the points of every
-// published column (what the harness needs to find where frame N + 1 starts, :205-209, and its two error conditions); k_scatter_apply
-// writes is_ground_point = (ground_point_label == GP_GROUND) and detection_label = id (:214-215) of the columns' points into the frames'
-// arrays in HBM, which cc_eval_frame_device then reads. grid = columns, block = 64 (lanes = rows).
-// =====================================================================================================
-__global__ __launch_bounds__(64) void k_scatter_info(Geometry g, Planes P, const StreamState* __restrict__ states, int s, long long from,
-                                                     const int* __restrict__ original_index, int slots, int* __restrict__ out_min,
-                                                     int* __restrict__ out_max)
-{
-    const SP p = stream_ptrs(P, g, s);
-    const int R = g.num_rows, RC = g.ring_cols, NC = g.num_columns;
-    const long long gc = from + blockIdx.x;
-    const int lc = (int) (gc % RC);
-    const int* org = original_index + (size_t) s * (size_t) slots * (size_t) NC * (size_t) R;
-    int mn = 0x7fffffff, mx = -1;
-    // only published columns that are still in the ring hold what this reads (anything else: "no point", like an empty column)
-    // (clearing is deferred by one call, so what a call published stays readable behind ring_start: the lower end is what has been CLEARED)
-    const bool live = gc >= 0 && gc >= states[s].clear_done && gc < states[s].first_unpublished;
-    for (int row = lane_id(); live && row < R; row += 64)
-    {
-        const int ci = lc * R + row;
-        if (p.dist[ci] == p.dist[ci]) // the cell holds a return
-        {
-            const unsigned seq = p.src[ci];
-            const int frame = (int) (seq / (unsigned) NC), col = (int) (seq % (unsigned) NC);
-            if (org[((size_t) (frame % slots) * NC + col) * R + row] >= 0)
-            {
-                mn = frame < mn ? frame : mn;
-                mx = frame > mx ? frame : mx;
-            }
-        }
-    }
-    mn = wave_min_i32(mn);
-    mx = -wave_min_i32(-mx);
-    if (lane_id() == 0)
-    {
-        out_min[blockIdx.x] = mn;
-        out_max[blockIdx.x] = mx;
-    }
-}
-
-__global__ __launch_bounds__(64) void k_scatter_apply(Geometry g, Planes P, const StreamState* __restrict__ states, int s, long long from,
-                                                      const int* __restrict__ original_index, int slots, unsigned char* __restrict__ is_ground,
-                                                      unsigned* __restrict__ detection, long long max_points)
-{
-    const SP p = stream_ptrs(P, g, s);
-    const int R = g.num_rows, RC = g.ring_cols, NC = g.num_columns;
-    const long long gc = from + blockIdx.x;
-    if (gc < 0 || gc < states[s].clear_done || gc >= states[s].first_unpublished)
-        return; // (not a published column of the live ring)
-    const int lc = (int) (gc % RC);
-    const int* org = original_index + (size_t) s * (size_t) slots * (size_t) NC * (size_t) R;
-    unsigned char* gr = is_ground + (size_t) s * (size_t) slots * (size_t) max_points;
-    unsigned* det = detection + (size_t) s * (size_t) slots * (size_t) max_points;
-    for (int row = lane_id(); row < R; row += 64)
-    {
-        const int ci = lc * R + row;
-        if (p.dist[ci] == p.dist[ci])
-        {
-            const unsigned seq = p.src[ci];
-            const int frame = (int) (seq / (unsigned) NC), col = (int) (seq % (unsigned) NC);
-            const int pt = org[((size_t) (frame % slots) * NC + col) * R + row];
-            if (pt >= 0 && pt < max_points)
-            {
-                const size_t o = (size_t) (frame % slots) * (size_t) max_points + (size_t) pt;
-                gr[o] = p.ground[ci] == CC_GP_GROUND ? 1 : 0;
-                // (the id as the takes read it, cc_k_take.h: k_take_write — not from Planes::id, which is only kept once a caller has asked for it)
-                const int r = p.root[ci];
-                det[o] = (r >= 0 && r < (int) g.cells) ? p.t_cid[r] : 0u;
-            }
         }
     }
 }

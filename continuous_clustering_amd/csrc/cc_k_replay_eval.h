@@ -1,11 +1,12 @@
-// cc_k_replay_eval.h — k_replay_poke, k_replay_plan, k_replay_info, k_replay_walk, k_replay_scan, k_replay_apply, k_replay_eval,
-// k_replay_compact: the frame scatter of the reference's harness (addColumnAndEvaluateFrameIfCompleted, kitti_demo.cpp:173-224) and the label
-// compare of the frames it completes (kitti_evaluation.cpp:29-146) for ALL streams of a replay engine per call (cc_replay_eval_step,
-// include/cc_kitti.h).
+// cc_k_replay_eval.h — the frame scatter of the reference's harness (addColumnAndEvaluateFrameIfCompleted, kitti_demo.cpp:173-224) for one
+// stream and a caller's columns (k_scatter_info, k_scatter_apply: cc_engine_scatter_*), and — k_replay_poke, k_replay_plan, k_replay_info,
+// k_replay_walk, k_replay_scan, k_replay_apply, k_replay_eval, k_replay_compact — the same scatter and the label compare of the frames it
+// completes (kitti_evaluation.cpp:29-146) for ALL streams of a replay engine per call (cc_replay_eval_step, include/cc_kitti.h, DESIGN.md
+// section 18).
 // (part of cc_kernels.h: included there, in order, inside namespace cck)
 //
-// Read-only on the engine's planes and on StreamState. The range of a stream is [max(cursor, clear_done, first_column), first_unpublished),
-// the bounds of k_take_plan; grids are sized by the host from the plan's longest range and from the number of completed frames, never from
+// Read-only on the engine's planes and on StreamState. The range of a stream is held_range (cc_k_held.h) from the stream's cursor up to
+// first_unpublished; grids are sized by the host from the plan's longest range and from the number of completed frames, never from
 // ring_cols x streams. Everything is integer: ballots, find-first-set, one exclusive scan over the streams, order-free atomics in the label
 // compare (ccev::eval_point, shared with cc_eval_frame_device). The entropies are summed on the host from the exact pair counts.
 #pragma once
@@ -69,6 +70,98 @@ __device__ __forceinline__ int replay_slot(const int frame, const int slots)
 }
 
 // =====================================================================================================
+// The frame scatter of the reference's harness (addColumnAndEvaluateFrameIfCompleted, kitti_demo.cpp:173-224) for a replayed KITTI sequence, on
+// the device. A stream that is fed exactly num_columns pseudo-firings per frame (kitti_demo.cpp:386-403) carries, per cell, the sequence number
+// of the firing that filled it: frame = sequence / num_columns, range-image column of the frame = sequence % num_columns, and the KITTI point of
+// the cell is original_index[frame % slots][column][row] (cc_kitti_frame::d_original_index of the frame's conversion). Both halves work on ONE
+// held column (ring slot lc of stream s) by one wavefront, lanes = rows; the single-stream kernels (cc_engine_scatter_info / _apply) and the
+// all-stream kernels (cc_replay_eval_step) below are wrappers that say which column.
+// =====================================================================================================
+// the smallest / largest frame among the points of the column (INT32_MAX / -1 for a column without points, or one that is not `live`): what the
+// harness needs to find where frame N + 1 starts (:205-209), and its two error conditions
+__device__ __forceinline__ void scatter_column_info(const Geometry& g, const SP& p, const int s, const int lc, const bool live,
+                                                    const int* __restrict__ original_index, const int slots, int* out_min, int* out_max)
+{
+    const int R = g.num_rows, NC = g.num_columns;
+    const int* org = original_index + (size_t) s * (size_t) slots * (size_t) NC * (size_t) R;
+    int mn = 0x7fffffff, mx = -1;
+    for (int row = lane_id(); live && row < R; row += 64)
+    {
+        const int ci = lc * R + row;
+        if (scatter_cell_has_return(p, ci))
+        {
+            const unsigned seq = p.src[ci];
+            const int frame = (int) (seq / (unsigned) NC), col = (int) (seq % (unsigned) NC);
+            if (org[((size_t) (frame % slots) * NC + col) * R + row] >= 0)
+            {
+                mn = frame < mn ? frame : mn;
+                mx = frame > mx ? frame : mx;
+            }
+        }
+    }
+    mn = wave_min_i32(mn);
+    mx = -wave_min_i32(-mx);
+    if (lane_id() == 0)
+    {
+        *out_min = mn;
+        *out_max = mx;
+    }
+}
+
+// is_ground_point = (ground_point_label == GP_GROUND) and detection_label = id (:214-215) of the column's points into the frames' arrays in
+// HBM, which the label compare then reads
+__device__ __forceinline__ void scatter_column_apply(const Geometry& g, const SP& p, const int s, const int lc, const int* __restrict__ original_index,
+                                                     const int slots, unsigned char* __restrict__ is_ground, unsigned* __restrict__ detection,
+                                                     const long long max_points)
+{
+    const int R = g.num_rows, NC = g.num_columns;
+    const int* org = original_index + (size_t) s * (size_t) slots * (size_t) NC * (size_t) R;
+    unsigned char* gr = is_ground + (size_t) s * (size_t) slots * (size_t) max_points;
+    unsigned* det = detection + (size_t) s * (size_t) slots * (size_t) max_points;
+    for (int row = lane_id(); row < R; row += 64)
+    {
+        const int ci = lc * R + row;
+        if (scatter_cell_has_return(p, ci))
+        {
+            const unsigned seq = p.src[ci];
+            const int frame = (int) (seq / (unsigned) NC), col = (int) (seq % (unsigned) NC);
+            const int pt = org[((size_t) (frame % slots) * NC + col) * R + row];
+            if (pt >= 0 && pt < max_points)
+            {
+                const size_t o = (size_t) (frame % slots) * (size_t) max_points + (size_t) pt;
+                gr[o] = p.ground[ci] == CC_GP_GROUND ? 1 : 0;
+                det[o] = cell_cluster_id(p, ci, (int) g.cells);
+            }
+        }
+    }
+}
+
+// =====================================================================================================
+// k_scatter_info / k_scatter_apply — the scatter for columns [from, from + grid) of ONE stream. grid = columns, block = 64. The caller names the
+// columns, so the kernels test them: only a published column that has not been cleared, clear_done <= column < first_unpublished, holds what this
+// reads (clearing is deferred by one call, so what a call published stays readable behind ring_start); anything else is "no point", like an
+// empty column.
+// =====================================================================================================
+__global__ __launch_bounds__(64) void k_scatter_info(Geometry g, Planes P, const StreamState* __restrict__ states, int s, long long from,
+                                                     const int* __restrict__ original_index, int slots, int* __restrict__ out_min,
+                                                     int* __restrict__ out_max)
+{
+    const long long gc = from + blockIdx.x;
+    const bool live = gc >= 0 && gc >= states[s].clear_done && gc < states[s].first_unpublished;
+    scatter_column_info(g, stream_ptrs(P, g, s), s, (int) (gc % g.ring_cols), live, original_index, slots, out_min + blockIdx.x, out_max + blockIdx.x);
+}
+
+__global__ __launch_bounds__(64) void k_scatter_apply(Geometry g, Planes P, const StreamState* __restrict__ states, int s, long long from,
+                                                      const int* __restrict__ original_index, int slots, unsigned char* __restrict__ is_ground,
+                                                      unsigned* __restrict__ detection, long long max_points)
+{
+    const long long gc = from + blockIdx.x;
+    if (gc < 0 || gc < states[s].clear_done || gc >= states[s].first_unpublished)
+        return; // (not a published column that is still held)
+    scatter_column_apply(g, stream_ptrs(P, g, s), s, (int) (gc % g.ring_cols), original_index, slots, is_ground, detection, max_points);
+}
+
+// =====================================================================================================
 // k_replay_poke — cc_replay_eval_seek / cc_replay_eval_set_active in stream order (no synchronisation). One thread.
 // =====================================================================================================
 __global__ void k_replay_poke(ReplayState* __restrict__ state, int s, int seek, long long column, int prev, int set_active, int active)
@@ -98,7 +191,7 @@ __global__ __launch_bounds__(64) void k_replay_plan(Geometry g, const StreamStat
         return;
     const StreamState* st = &states[s];
     const ReplayState rs = state[s];
-    const long long first = st->first_column, cleared = st->clear_done, upper = st->first_unpublished;
+    const long long first = st->first_column, upper = st->first_unpublished;
     cc_replay_stream t;
     t.col_from = t.col_to = rs.cursor;
     t.lost_columns = 0;
@@ -109,14 +202,10 @@ __global__ __launch_bounds__(64) void k_replay_plan(Geometry g, const StreamStat
     t.active = rs.active;
     if (t.error == 0 && rs.active != 0 && first >= 0 && upper >= 0)
     {
-        const long long base = rs.cursor > first ? rs.cursor : first; // (columns in front of the stream's first one never existed: not lost)
-        long long from = base > cleared ? base : cleared;
-        const long long to = upper > from ? upper : from;             // (a cursor that was sought past `upper` stays where it is)
-        if (to - from > g.ring_cols)
-            from = to - g.ring_cols;                                    // (never: the ring holds no more)
-        t.col_from = from;
-        t.col_to = to;
-        t.lost_columns = from - base;
+        const HeldRange r = held_range(first, st->clear_done, upper, rs.cursor, g.ring_cols);
+        t.col_from = r.from;
+        t.col_to = r.to;
+        t.lost_columns = r.lost;
     }
     plan[s] = t;
     h_plan[s] = t;
@@ -124,44 +213,17 @@ __global__ __launch_bounds__(64) void k_replay_plan(Geometry g, const StreamStat
 }
 
 // =====================================================================================================
-// k_replay_info — k_scatter_info's body for the planned ranges of all streams: the smallest / largest frame among the points of a column
-// (INT32_MAX / -1 for a column without points). grid = (longest range, streams), block = 64: one wavefront per (column, stream), lanes = rows
+// k_replay_info — scatter_column_info over the planned ranges of all streams. grid = (longest range, streams), block = 64: one wavefront per (column, stream), lanes = rows
 // (two trips at 128 rows). out_min / out_max [s * stride + c] belong to column col_from + c.
 // =====================================================================================================
 __global__ __launch_bounds__(64) void k_replay_info(Geometry g, Planes P, const cc_replay_stream* __restrict__ plan, const int* __restrict__ original_index,
                                                     int slots, int* __restrict__ out_min, int* __restrict__ out_max, int stride)
 {
-    const int s = (int) blockIdx.y, c = (int) blockIdx.x;
-    const long long from = uniform_i64(plan[s].col_from), to = uniform_i64(plan[s].col_to);
-    if (c >= to - from || c >= stride)
+    HeldColumn h;
+    if (!held_column(g, P, plan, stride, &h))
         return;
-    const SP p = stream_ptrs(P, g, s);
-    const int R = g.num_rows, RC = g.ring_cols, NC = g.num_columns;
-    const long long gc = from + c;
-    const int lc = (int) (gc % RC);
-    const int* org = original_index + (size_t) s * (size_t) slots * (size_t) NC * (size_t) R;
-    int mn = 0x7fffffff, mx = -1;
-    for (int row = lane_id(); row < R; row += 64)
-    {
-        const int ci = lc * R + row;
-        if (p.dist[ci] == p.dist[ci]) // the cell holds a return
-        {
-            const unsigned seq = p.src[ci];
-            const int frame = (int) (seq / (unsigned) NC), col = (int) (seq % (unsigned) NC);
-            if (org[((size_t) (frame % slots) * NC + col) * R + row] >= 0)
-            {
-                mn = frame < mn ? frame : mn;
-                mx = frame > mx ? frame : mx;
-            }
-        }
-    }
-    mn = wave_min_i32(mn);
-    mx = -wave_min_i32(-mx);
-    if (lane_id() == 0)
-    {
-        out_min[(size_t) s * stride + c] = mn;
-        out_max[(size_t) s * stride + c] = mx;
-    }
+    const size_t o = (size_t) h.s * stride + h.c;
+    scatter_column_info(g, h.p, h.s, h.lc, true, original_index, slots, out_min + o, out_max + o);
 }
 
 // =====================================================================================================
@@ -271,16 +333,15 @@ __global__ __launch_bounds__(TAKE_SCAN_THREADS) void k_replay_scan(int num_strea
 {
     __shared__ long long s_buf[TAKE_SCAN_THREADS];
     const int t = (int) threadIdx.x;
-    const int per = (num_streams + TAKE_SCAN_THREADS - 1) / TAKE_SCAN_THREADS;
-    const int b = t * per < num_streams ? t * per : num_streams;
-    const int e = b + per < num_streams ? b + per : num_streams;
+    long long b, e;
+    run_of(t, num_streams, &b, &e);
     long long sum = 0;
-    for (int i = b; i < e; i++)
+    for (long long i = b; i < e; i++)
         sum += walk[i].n_done;
     long long total;
     long long off = take_block_scan(s_buf, sum, &total);
     const bool fits = total <= capacity && total <= job_capacity;
-    for (int i = b; i < e; i++)
+    for (int i = (int) b; i < e; i++)
     {
         const ReplayWalk w = walk[i];
         cc_replay_stream r = plan[i];
@@ -331,9 +392,8 @@ __global__ __launch_bounds__(TAKE_SCAN_THREADS) void k_replay_scan(int num_strea
 }
 
 // =====================================================================================================
-// k_replay_apply — k_scatter_apply's body for the applied ranges [col_from, col_to) of all streams (col_to is the walk's apply-to column by
-// now): is_ground_point = (ground_point_label == GP_GROUND) and detection_label = id (kitti_demo.cpp:214-215) of the columns' points into the
-// frames' slots. Nothing is written unless every record fits. grid = (longest range, streams), block = 64.
+// k_replay_apply — scatter_column_apply over the applied ranges [col_from, col_to) of all streams (col_to is the walk's apply-to column by
+// now). Nothing is written unless every record fits. grid = (longest range, streams), block = 64.
 // =====================================================================================================
 __global__ __launch_bounds__(64) void k_replay_apply(Geometry g, Planes P, const cc_replay_stream* __restrict__ plan, const ReplayCtl* __restrict__ ctl,
                                                      const int* __restrict__ original_index, int slots, unsigned char* __restrict__ is_ground,
@@ -341,35 +401,10 @@ __global__ __launch_bounds__(64) void k_replay_apply(Geometry g, Planes P, const
 {
     if (uniform_i32(ctl->fits) == 0)
         return; // (all or nothing)
-    const int s = (int) blockIdx.y, c = (int) blockIdx.x;
-    const long long from = uniform_i64(plan[s].col_from), to = uniform_i64(plan[s].col_to);
-    if (c >= to - from)
+    HeldColumn h;
+    if (!held_column(g, P, plan, 0x7fffffff, &h)) // (no per-stream array)
         return;
-    const SP p = stream_ptrs(P, g, s);
-    const int R = g.num_rows, RC = g.ring_cols, NC = g.num_columns;
-    const long long gc = from + c;
-    const int lc = (int) (gc % RC);
-    const int* org = original_index + (size_t) s * (size_t) slots * (size_t) NC * (size_t) R;
-    unsigned char* gr = is_ground + (size_t) s * (size_t) slots * (size_t) max_points;
-    unsigned* det = detection + (size_t) s * (size_t) slots * (size_t) max_points;
-    for (int row = lane_id(); row < R; row += 64)
-    {
-        const int ci = lc * R + row;
-        if (p.dist[ci] == p.dist[ci])
-        {
-            const unsigned seq = p.src[ci];
-            const int frame = (int) (seq / (unsigned) NC), col = (int) (seq % (unsigned) NC);
-            const int pt = org[((size_t) (frame % slots) * NC + col) * R + row];
-            if (pt >= 0 && pt < max_points)
-            {
-                const size_t o = (size_t) (frame % slots) * (size_t) max_points + (size_t) pt;
-                gr[o] = p.ground[ci] == CC_GP_GROUND ? 1 : 0;
-                // (the id as the takes read it, cc_k_take.h: k_take_write — not from Planes::id, which is only kept once a caller has asked for it)
-                const int r = p.root[ci];
-                det[o] = (r >= 0 && r < (int) g.cells) ? p.t_cid[r] : 0u;
-            }
-        }
-    }
+    scatter_column_apply(g, h.p, h.s, h.lc, original_index, slots, is_ground, detection, max_points);
 }
 
 // =====================================================================================================

@@ -3,14 +3,11 @@
 // (part of cc_kernels.h: included there, in order, inside namespace cck)
 //
 // Read-only on the engine's planes and on StreamState; the only engine state they write is the cursor array, and that only when every record
-// fit. The range of a stream is [max(cursor, clear_done, first_column), upper): columns below StreamState::clear_done have been cleared
-// physically, everything from there up to first_unpublished (first_unfinished) is what the publishing (segmentation) chain left and nobody
-// changes any more — the same bounds k_scatter_info / k_scatter_apply rely on. Counts are integers from __ballot + popcount and every record's
-// place follows from two exclusive scans, so the output does not depend on scheduling. Grids are sized by the host from the plan's longest range.
+// fit. The range of a stream is held_range (cc_k_held.h) from the stream's cursor up to first_unpublished (first_unfinished). Counts are
+// integers from __ballot + popcount and every record's place follows from two exclusive scans (run_of, take_block_scan), so the output does not
+// depend on scheduling. Grids are sized by the host from the plan's longest range.
 #pragma once
 
-constexpr int TAKE_SCAN_THREADS = 256;
-static_assert(sizeof(cc_take_point) == 32 && alignof(cc_take_point) == 4, "a record is two 16-byte stores");
 static_assert(sizeof(cc_take_stream) == 48, "include/cc_hip.h: one table entry per stream");
 
 struct TakeCtl
@@ -20,25 +17,6 @@ struct TakeCtl
     int fits;           // total <= capacity and the caller gave a record array: k_take_write writes and moves the cursors
     int pad;
 };
-
-// exclusive scan of one value per thread over a block of TAKE_SCAN_THREADS threads (Hillis-Steele in LDS); *total = the sum, to every thread
-__device__ __forceinline__ long long take_block_scan(long long* s_buf, const long long v, long long* total)
-{
-    const int t = (int) threadIdx.x;
-    s_buf[t] = v;
-    __syncthreads();
-    for (int d = 1; d < TAKE_SCAN_THREADS; d <<= 1)
-    {
-        const long long add = t >= d ? s_buf[t - d] : 0ll;
-        __syncthreads();
-        s_buf[t] += add;
-        __syncthreads();
-    }
-    const long long incl = s_buf[t];
-    *total = s_buf[TAKE_SCAN_THREADS - 1];
-    __syncthreads(); // (s_buf may be filled again)
-    return incl - v;
-}
 
 // =====================================================================================================
 // k_take_plan — per stream: the range a take hands over, what was lost in front of it, the stream's error. One thread per stream; the table goes
@@ -52,7 +30,7 @@ __global__ __launch_bounds__(64) void k_take_plan(Geometry g, const StreamState*
         return;
     const StreamState* st = &states[s];
     const long long cursor = cursors[(size_t) stage * g.num_streams + s];
-    const long long first = st->first_column, cleared = st->clear_done;
+    const long long first = st->first_column;
     const long long upper = stage == CC_TAKE_CLUSTERED ? st->first_unpublished : st->first_unfinished;
     cc_take_stream t;
     t.col_from = t.col_to = cursor;
@@ -62,34 +40,25 @@ __global__ __launch_bounds__(64) void k_take_plan(Geometry g, const StreamState*
     t.pad = 0;
     if (t.error == 0 && first >= 0 && upper >= 0)
     {
-        const long long base = cursor > first ? cursor : first; // (columns in front of the stream's first one never existed: not lost)
-        long long from = base > cleared ? base : cleared;
-        const long long to = upper > from ? upper : from;       // (a cursor that was sought past `upper` stays where it is)
-        if (to - from > g.ring_cols)
-            from = to - g.ring_cols;                              // (never: the ring holds no more)
-        t.col_from = from;
-        t.col_to = to;
-        t.lost_columns = from - base;
+        const HeldRange r = held_range(first, st->clear_done, upper, cursor, g.ring_cols);
+        t.col_from = r.from;
+        t.col_to = r.to;
+        t.lost_columns = r.lost;
     }
     plan[s] = t;
     h_plan[s] = t;
     __threadfence_system();
 }
 
-// is cell ci (row `row` of a column whose pass over the ring has tag `tag`) handed over? view_column's rule for "the cell holds a return"
-// (cc_k_publish.h), then the caller's selection
+// is cell ci (row `row` of a column whose pass over the ring has tag `tag`) handed over? It holds a return, then the caller's selection
 __device__ __forceinline__ bool take_selects(const SP& p, const int ci, const uint16_t tag, const int select, const int cells)
 {
-    const float d = p.dist[ci];
-    if (!(p.gtag[ci] == tag && d == d))
+    if (!cell_has_return(p, ci, tag))
         return false;
     if (select == CC_TAKE_NOT_GROUND)
         return p.ground[ci] != (uint8_t) CC_GP_GROUND;
     if (select == CC_TAKE_WITH_ID)
-    {
-        const int r = p.root[ci];
-        return r >= 0 && r < cells && p.t_cid[r] != 0u;
-    }
+        return cell_cluster_id(p, ci, cells) != 0u;
     return true;
 }
 
@@ -100,24 +69,19 @@ __device__ __forceinline__ bool take_selects(const SP& p, const int ci, const ui
 __global__ __launch_bounds__(64) void k_take_count(Geometry g, Planes P, const cc_take_stream* __restrict__ plan, int select, unsigned* __restrict__ counts,
                                                    int stride)
 {
-    const int s = (int) blockIdx.y, c = (int) blockIdx.x;
-    const long long from = uniform_i64(plan[s].col_from), to = uniform_i64(plan[s].col_to);
-    if (c >= to - from || c >= stride)
+    HeldColumn h;
+    if (!held_column(g, P, plan, stride, &h))
         return;
-    const SP p = stream_ptrs(P, g, s);
-    const int R = g.num_rows, RC = g.ring_cols, lane = lane_id();
-    const long long gc = from + c;
-    const int lc = (int) (gc % RC);
-    const uint16_t tag = cell_tag(gc / RC);
+    const int R = g.num_rows, lane = lane_id();
     int n = 0;
     for (int r0 = 0; r0 < R; r0 += 64)
     {
         const int row = r0 + lane;
-        const bool sel = row < R && take_selects(p, lc * R + row, tag, select, (int) g.cells);
+        const bool sel = row < R && take_selects(h.p, h.lc * R + row, h.tag, select, (int) g.cells);
         n += (int) __popcll(__ballot(sel));
     }
     if (lane == 0)
-        counts[(size_t) s * stride + c] = (unsigned) n;
+        counts[(size_t) h.s * stride + h.c] = (unsigned) n;
 }
 
 // =====================================================================================================
@@ -132,9 +96,8 @@ __global__ __launch_bounds__(TAKE_SCAN_THREADS) void k_take_scan(cc_take_stream*
     long long len = plan[s].col_to - plan[s].col_from;
     len = len > stride ? stride : len;
     unsigned* cnt = counts + (size_t) s * stride;
-    const long long per = (len + TAKE_SCAN_THREADS - 1) / TAKE_SCAN_THREADS;
-    const long long b = (long long) t * per < len ? (long long) t * per : len;
-    const long long e = b + per < len ? b + per : len;
+    long long b, e;
+    run_of(t, len, &b, &e);
     long long sum = 0;
     for (long long i = b; i < e; i++)
         sum += cnt[i];
@@ -160,15 +123,14 @@ __global__ __launch_bounds__(TAKE_SCAN_THREADS) void k_take_scan_streams(int num
 {
     __shared__ long long s_buf[TAKE_SCAN_THREADS];
     const int t = (int) threadIdx.x;
-    const int per = (num_streams + TAKE_SCAN_THREADS - 1) / TAKE_SCAN_THREADS;
-    const int b = t * per < num_streams ? t * per : num_streams;
-    const int e = b + per < num_streams ? b + per : num_streams;
+    long long b, e;
+    run_of(t, num_streams, &b, &e);
     long long sum = 0;
-    for (int i = b; i < e; i++)
+    for (long long i = b; i < e; i++)
         sum += plan[i].n_records;
     long long total;
     long long off = take_block_scan(s_buf, sum, &total);
-    for (int i = b; i < e; i++)
+    for (long long i = b; i < e; i++)
     {
         cc_take_stream r = plan[i];
         r.first_record = off;
@@ -202,51 +164,28 @@ __global__ __launch_bounds__(64) void k_take_write(Geometry g, Planes P, const c
 {
     if (uniform_i32(ctl->fits) == 0)
         return; // (all or nothing)
-    const int s = (int) blockIdx.y, c = (int) blockIdx.x;
+    const int s = (int) blockIdx.y;
     const int lane = lane_id();
-    const long long from = uniform_i64(plan[s].col_from), to = uniform_i64(plan[s].col_to);
-    if (c == 0 && lane == 0 && plan[s].error == 0)
-        cursors[(size_t) stage * g.num_streams + s] = to; // (no block of this launch reads the cursors: the ranges come from the plan)
-    if (c >= to - from || c >= stride)
+    if (blockIdx.x == 0 && lane == 0 && plan[s].error == 0)
+        cursors[(size_t) stage * g.num_streams + s] = plan[s].col_to; // (no block of this launch reads the cursors: the ranges come from the plan)
+    HeldColumn h;
+    if (!held_column(g, P, plan, stride, &h))
         return;
-    const SP p = stream_ptrs(P, g, s);
-    const int R = g.num_rows, RC = g.ring_cols;
+    const SP& p = h.p;
+    const int R = g.num_rows;
     const long long capacity = uniform_i64(ctl->capacity);
-    const long long gc = from + c;
-    const int lc = (int) (gc % RC);
-    const uint16_t tag = cell_tag(gc / RC);
-    long long pos = uniform_i64(plan[s].first_record) + (long long) counts[(size_t) s * stride + c];
+    long long pos = uniform_i64(plan[s].first_record) + (long long) counts[(size_t) s * stride + h.c];
     for (int r0 = 0; r0 < R; r0 += 64)
     {
         const int row = r0 + lane;
-        const int ci = lc * R + row;
-        const bool sel = row < R && take_selects(p, ci, tag, select, (int) g.cells);
+        const int ci = h.lc * R + row;
+        const bool sel = row < R && take_selects(p, ci, h.tag, select, (int) g.cells);
         const unsigned long long mask = __ballot(sel);
         if (sel)
         {
             const long long o = pos + __popcll(mask & lanes_below());
             if (o < capacity) // (always, when the verdict was "fits"; an index is checked where it is used)
-            {
-                const float4 rec = p.sc_rec[ci];
-                unsigned id = 0u;
-                if (stage == CC_TAKE_CLUSTERED)
-                {
-                    const int r = p.root[ci];
-                    id = (r >= 0 && r < (int) g.cells) ? p.t_cid[r] : 0u;
-                }
-                uint4 lo, hi;
-                lo.x = __float_as_uint(rec.x);
-                lo.y = __float_as_uint(rec.y);
-                lo.z = __float_as_uint(rec.z);
-                lo.w = __float_as_uint(p.dist[ci]);
-                hi.x = id;
-                hi.y = p.src[ci];
-                hi.z = (unsigned) row | ((unsigned) p.ground[ci] << 16) | ((unsigned) p.inten[ci] << 24);
-                hi.w = (unsigned) c;
-                uint4* out = (uint4*) (records + o);
-                out[0] = lo;
-                out[1] = hi;
-            }
+                store_take_point(records + o, p, ci, row, stage == CC_TAKE_CLUSTERED ? cell_cluster_id(p, ci, (int) g.cells) : 0u, (unsigned) h.c);
         }
         pos += __popcll(mask);
     }

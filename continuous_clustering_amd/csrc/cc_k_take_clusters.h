@@ -6,8 +6,9 @@
 // Read-only on the engine's planes and on StreamState; the only engine state they write is the (ids taken, floor) pair per stream, and that
 // only when every descriptor and record fit. Cluster ids are a counter (StreamState::cluster_counter, cc.cpp:939), so "finished since the last
 // take" is the id range [next_id, cluster_counter) and a cluster's slot in the aggregate table is id - id_from: no events, no search. A cell
-// of a column below first_unfinished belongs to cluster c iff it holds a return (take_selects' rule) and the root of its tree is finished and
-// carries c — what k_gather_clusters relies on, also for columns that are not published yet. Counts are integer atomics (one set per column
+// of a column below first_unfinished belongs to cluster c iff it holds a return (cell_has_return, cc_k_held.h) and the root of its tree is
+// finished and carries c (cell_cluster_id) — what k_gather_clusters relies on, also for columns that are not published yet. The columns come from
+// held_range, from the stream's floor up to first_unfinished. Counts are integer atomics (one set per column
 // and cluster, all order-free); every place in the output follows from exclusive scans, so the output does not depend on scheduling. Grids
 // are sized by the host from the plan.
 #pragma once
@@ -44,53 +45,15 @@ struct TcCtl
     int pad;
 };
 
-__device__ __forceinline__ float wave_min_f32(float v)
-{
-    int b = __float_as_int(v);
-    const int fill = 0x7f800000; // +inf
-#define CC_LESS_F32(a, b) (__int_as_float(a) < __int_as_float(b))
-    CC_DPP_REDUCE(int, dpp_mov_i32, b, fill, CC_LESS_F32)
-#undef CC_LESS_F32
-    return __int_as_float(__builtin_amdgcn_readlane(b, 63));
-}
-__device__ __forceinline__ float wave_max_f32(float v)
-{
-    int b = __float_as_int(v);
-    const int fill = (int) 0xff800000u; // -inf
-#define CC_GREATER_F32(a, b) (__int_as_float(a) > __int_as_float(b))
-    CC_DPP_REDUCE(int, dpp_mov_i32, b, fill, CC_GREATER_F32)
-#undef CC_GREATER_F32
-    return __int_as_float(__builtin_amdgcn_readlane(b, 63));
-}
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v)
-{
-    int b = (int) v;
-    const int fill = -1;
-#define CC_LESS_U32(a, b) ((unsigned) (a) < (unsigned) (b))
-    CC_DPP_REDUCE(int, dpp_mov_i32, b, fill, CC_LESS_U32)
-#undef CC_LESS_U32
-    return (unsigned) __builtin_amdgcn_readlane(b, 63);
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v)
-{
-    int b = (int) v;
-    const int fill = 0;
-#define CC_GREATER_U32(a, b) ((unsigned) (a) > (unsigned) (b))
-    CC_DPP_REDUCE(int, dpp_mov_i32, b, fill, CC_GREATER_U32)
-#undef CC_GREATER_U32
-    return (unsigned) __builtin_amdgcn_readlane(b, 63);
-}
-
 // the id of the finished cluster cell ci belongs to, if that id is one of [id_from, id_to); else 0
 __device__ __forceinline__ unsigned tc_member_id(const SP& p, const int ci, const uint16_t tag, const int cells, const long long id_from, const long long id_to)
 {
-    const float d = p.dist[ci];
-    if (!(p.gtag[ci] == tag && d == d))
+    if (!cell_has_return(p, ci, tag))
         return 0u;
-    const int r = p.root[ci];
-    if (r < 0 || r >= cells || !p.t_finished[r])
+    const int r = cell_root(p, ci, cells);
+    if (r < 0 || !p.t_finished[r])
         return 0u;
-    const unsigned id = p.t_cid[r];
+    const unsigned id = cell_cluster_id(p, ci, cells);
     return ((long long) id >= id_from && (long long) id < id_to) ? id : 0u;
 }
 
@@ -105,11 +68,10 @@ __global__ __launch_bounds__(TAKE_SCAN_THREADS) void k_tc_plan(Geometry g, const
 {
     __shared__ long long s_buf[TAKE_SCAN_THREADS];
     const int S = g.num_streams, t = (int) threadIdx.x;
-    const int per = (S + TAKE_SCAN_THREADS - 1) / TAKE_SCAN_THREADS;
-    const int b = t * per < S ? t * per : S;
-    const int e = b + per < S ? b + per : S;
+    long long b, e;
+    run_of(t, S, &b, &e);
     long long sum = 0;
-    for (int s = b; s < e; s++)
+    for (long long s = b; s < e; s++)
     {
         const StreamState* st = &states[s];
         const long long taken = cursors[2 * s], floor = cursors[2 * s + 1];
@@ -132,17 +94,13 @@ __global__ __launch_bounds__(TAKE_SCAN_THREADS) void k_tc_plan(Geometry g, const
             if (id_to - pl.id_from > TC_MAX_IDS)
                 pl.id_from = id_to - TC_MAX_IDS; // (an engine nobody took from for thousands of clusters: the newest)
             pl.n_ids = (int) (id_to - pl.id_from);
-            const long long base = floor > first ? floor : first; // (columns in front of the stream's first one never existed: not lost)
-            long long from = base > cleared ? base : cleared;
             // (columns from first_unfinished up have not been associated: their cells' roots are what the previous pass over the ring left, and no
             // finished cluster reaches them — view_column's rule for a cell's id)
-            long long to = st->first_unfinished < st->ring_end + 1 ? st->first_unfinished : st->ring_end + 1;
-            to = to > from ? to : from;
-            if (to - from > g.ring_cols)
-                from = to - g.ring_cols;                            // (never: the ring holds no more)
-            r.lost_columns = from - base;
-            pl.col_from = from;
-            pl.col_to = pl.n_ids > 0 ? to : from;                   // (no id to look for: no column to walk)
+            const long long upper = st->first_unfinished < st->ring_end + 1 ? st->first_unfinished : st->ring_end + 1;
+            const HeldRange hr = held_range(first, cleared, upper, floor, g.ring_cols);
+            r.lost_columns = hr.lost;
+            pl.col_from = hr.from;
+            pl.col_to = pl.n_ids > 0 ? hr.to : hr.from;             // (no id to look for: no column to walk)
             pl.ids_taken = id_to - 1;
             pl.floor = st->first_unpublished > floor ? st->first_unpublished : floor;
         }
@@ -154,7 +112,7 @@ __global__ __launch_bounds__(TAKE_SCAN_THREADS) void k_tc_plan(Geometry g, const
     }
     long long total;
     long long off = take_block_scan(s_buf, sum, &total);
-    for (int s = b; s < e; s++)
+    for (long long s = b; s < e; s++)
     {
         plan[s].base = (int) off; // (the host refuses a total beyond INT_MAX before any kernel uses a base)
         off += plan[s].n_ids;
@@ -194,21 +152,17 @@ __global__ __launch_bounds__(TAKE_SCAN_THREADS) void k_tc_clear(const TcPlan* __
 __global__ __launch_bounds__(64) void k_tc_mark(Geometry g, Planes P, const TcPlan* __restrict__ plan, const cc_take_cluster_stream* __restrict__ table,
                                                 TcSlot* __restrict__ slots, long long n_slots)
 {
-    const int s = (int) blockIdx.y, c = (int) blockIdx.x;
-    const long long from = uniform_i64(plan[s].col_from), to = uniform_i64(plan[s].col_to);
-    if (c >= to - from)
+    HeldColumn h;
+    if (!held_column(g, P, plan, 0x7fffffff, &h)) // (no per-stream array: the slots go by id)
         return;
+    const int s = h.s, c = h.c;
     const long long id_from = uniform_i64(table[s].id_from), id_to = uniform_i64(table[s].id_to);
     const int base = uniform_i32(plan[s].base), n_ids = uniform_i32(plan[s].n_ids);
-    const SP p = stream_ptrs(P, g, s);
-    const int R = g.num_rows, RC = g.ring_cols, lane = lane_id();
-    const long long gc = from + c;
-    const int lc = (int) (gc % RC);
-    const uint16_t tag = cell_tag(gc / RC);
+    const int R = g.num_rows, lane = lane_id();
     for (int r0 = 0; r0 < R; r0 += 64)
     {
         const int row = r0 + lane;
-        const unsigned id = row < R ? tc_member_id(p, lc * R + row, tag, (int) g.cells, id_from, id_to) : 0u;
+        const unsigned id = row < R ? tc_member_id(h.p, h.lc * R + row, h.tag, (int) g.cells, id_from, id_to) : 0u;
         unsigned long long todo = __ballot(id != 0u);
         while (todo)
         {
@@ -242,9 +196,8 @@ __global__ __launch_bounds__(TAKE_SCAN_THREADS) void k_tc_scan(const TcPlan* __r
     len = plan[s].base + len > n_slots ? n_slots - plan[s].base : len;
     len = len > 0 ? len : 0;
     TcSlot* sl = slots + plan[s].base;
-    const long long per = (len + TAKE_SCAN_THREADS - 1) / TAKE_SCAN_THREADS;
-    const long long b = (long long) t * per < len ? (long long) t * per : len;
-    const long long e = b + per < len ? b + per : len;
+    long long b, e;
+    run_of(t, len, &b, &e);
     long long n_keep = 0, n_rec = 0;
     for (long long i = b; i < e; i++)
         if (sl[i].count >= need)
@@ -280,11 +233,10 @@ __global__ __launch_bounds__(TAKE_SCAN_THREADS) void k_tc_scan_streams(int num_s
 {
     __shared__ long long s_buf[TAKE_SCAN_THREADS];
     const int t = (int) threadIdx.x;
-    const int per = (num_streams + TAKE_SCAN_THREADS - 1) / TAKE_SCAN_THREADS;
-    const int b = t * per < num_streams ? t * per : num_streams;
-    const int e = b + per < num_streams ? b + per : num_streams;
+    long long b, e;
+    run_of(t, num_streams, &b, &e);
     long long n_cl = 0, n_rec = 0;
-    for (int i = b; i < e; i++)
+    for (long long i = b; i < e; i++)
     {
         n_cl += table[i].n_clusters;
         n_rec += table[i].n_records;
@@ -292,7 +244,7 @@ __global__ __launch_bounds__(TAKE_SCAN_THREADS) void k_tc_scan_streams(int num_s
     long long total_cl, total_rec;
     long long k = take_block_scan(s_buf, n_cl, &total_cl);
     long long o = take_block_scan(s_buf, n_rec, &total_rec);
-    for (int i = b; i < e; i++)
+    for (long long i = b; i < e; i++)
     {
         cc_take_cluster_stream r = table[i];
         r.first_cluster = (int) k;
@@ -394,20 +346,7 @@ __global__ __launch_bounds__(64) void k_tc_write(Geometry g, Planes P, const TcP
                 f_max = src > f_max ? src : f_max;
                 const long long o = pos + __popcll(mask & lanes_below());
                 if (records && o < end && o < record_capacity) // (always, when the verdict was "fits"; an index is checked where it is used)
-                {
-                    uint4 lo, hi;
-                    lo.x = __float_as_uint(rec.x);
-                    lo.y = __float_as_uint(rec.y);
-                    lo.z = __float_as_uint(rec.z);
-                    lo.w = __float_as_uint(p.dist[ci]);
-                    hi.x = id;
-                    hi.y = src;
-                    hi.z = (unsigned) row | ((unsigned) p.ground[ci] << 16) | ((unsigned) p.inten[ci] << 24);
-                    hi.w = (unsigned) (c - col_min);
-                    uint4* out = (uint4*) (records + o);
-                    out[0] = lo;
-                    out[1] = hi;
-                }
+                    store_take_point(records + o, p, ci, row, id, (unsigned) (c - col_min));
             }
             pos += __popcll(mask);
         }

@@ -16,11 +16,14 @@
 //   cc_k_assoc_lds.h     k_assoc_lds (one-wavefront serial association)
 //   cc_assoc_shared.h, cc_assoc3.h   k_assoc3: three / four cooperating wavefronts per stream, the exact serial kernel behind k_assocb
 //   cc_assocb.h          k_assocb: batch-parallel association + finished-cluster check (groups of columns, pipelined, points packed into lanes)
-//   cc_k_publish.h       k_publish, k_small_tail, frame scatter, cluster gathering, host view
-//   cc_k_take.h          k_take_plan / count / scan / write: the published points of all streams, compacted in device memory
+//   cc_k_held.h          what a reader of held columns needs: held_range / held_from (also host code, and g++ alone: tests/csrc/held_range_probe.cpp),
+//                        HeldColumn, a cell's return and cluster id, the 32-byte point record, run_of + take_block_scan
+//   cc_k_publish.h       k_publish, k_publish_backlog, k_small_tail, k_small_all, k_resident, cluster gathering, host view
+//   cc_k_take.h         k_take_plan / count / scan / write: the published points of all streams, compacted in device memory
 //   cc_k_take_clusters.h k_tc_plan / clear / mark / scan / write: the finished clusters of all streams, descriptors and grouped points in device memory
 //   cc_k_reset.h         k_reset_streams: reset(num_rows) for a list of streams, the other streams untouched
-//   cc_k_replay_eval.h   k_replay_plan / info / walk / scan / apply / eval / compact: frame scatter and label compare of replayed frames, all streams per call
+//   cc_k_replay_eval.h   the frame scatter of a replayed sequence: k_scatter_info / apply (one stream, the caller's columns) and
+//                        k_replay_plan / info / walk / scan / apply / eval / compact (scatter and label compare, all streams per call)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,6 +48,7 @@ using namespace ccd;
 #include "cc_assoc_shared.h"
 #include "cc_assoc3.h"
 #include "cc_assocb.h"
+#include "cc_k_held.h"
 #include "cc_k_publish.h"
 #include "cc_k_take.h"
 #include "cc_k_take_clusters.h"

@@ -1,6 +1,8 @@
-// cc_replay_eval.h — host side of the replay evaluator (cc_replay_eval_*, include/cc_kitti.h; kernels: cc_k_replay_eval.h).
+// cc_replay_eval.h — host side of the frame scatter of a replayed sequence: per stream and for the caller's columns (cc_engine_scatter_info /
+// _apply), and for all streams per call with the label compare behind it, the replay evaluator (cc_replay_eval_*). ABI: include/cc_kitti.h;
+// kernels: cc_k_replay_eval.h, where both paths share scatter_column_info / scatter_column_apply; DESIGN.md sections 9 and 18.
 // Not a header of its own: cc_engine.hip includes it once, at its end, behind everything it calls (cc_engine, CC_HIP_CHECK, stop_resident,
-// finish_batch). The handle owns all of its memory from create to destroy; a step enqueues on the engine's stream and counts its own kernel
+// finish_batch, ensure_gather). The evaluator's handle owns all of its memory from create to destroy; a step enqueues on the engine's stream and counts its own kernel
 // launches and synchronisations.
 
 struct cc_replay_eval
@@ -184,6 +186,70 @@ int replay_enter(cc_replay_eval* h, const char* who, bool finish)
 } // namespace
 
 extern "C" {
+
+// ---- frame scatter of a replayed sequence (kitti_demo.cpp:173-224), include/cc_kitti.h ------------------------------------------------
+int cc_engine_scatter_info(cc_engine* e, int n, const int32_t* streams, const int64_t* from, const int64_t* to, const int32_t* d_original_index,
+                           int slots, int32_t* h_min_frame, int32_t* h_max_frame)
+{
+    if (!e || n < 0 || slots < 1 || (n > 0 && (!streams || !from || !to || !d_original_index || !h_min_frame || !h_max_frame)))
+        return CC_ERR_INVALID_ARGUMENT;
+    (void) hipSetDevice(e->device);
+    int rc = stop_resident(e);
+    if (rc)
+        return rc;
+    rc = finish_batch(e);
+    if (rc)
+        return rc;
+    size_t total = 0;
+    for (int i = 0; i < n; i++)
+    {
+        if (streams[i] < 0 || streams[i] >= e->g.num_streams || from[i] < 0 || to[i] - from[i] >= e->g.ring_cols)
+            return CC_ERR_INVALID_ARGUMENT; // (columns outside the stream's published ring window read as empty: the kernels check)
+        if (to[i] >= from[i])
+            total += (size_t) (to[i] - from[i] + 1);
+    }
+    if (total == 0)
+        return CC_OK;
+    if ((rc = ensure_gather(e, total * 8 + 64)))
+        return rc;
+    int* d_min = (int*) e->d_gather;
+    int* d_max = d_min + total;
+    size_t o = 0;
+    for (int i = 0; i < n; i++)
+        if (to[i] >= from[i])
+        {
+            const unsigned cols = (unsigned) (to[i] - from[i] + 1);
+            hipLaunchKernelGGL(cck::k_scatter_info, dim3(cols), dim3(64), 0, e->stream, e->g, e->P, (const StreamState*) e->d_states, streams[i], (long long) from[i], d_original_index,
+                               slots, d_min + o, d_max + o);
+            o += cols;
+        }
+    CC_HIP_CHECK(e, hipGetLastError());
+    CC_HIP_CHECK(e, hipMemcpyAsync(h_min_frame, d_min, total * 4, hipMemcpyDeviceToHost, e->stream));
+    CC_HIP_CHECK(e, hipMemcpyAsync(h_max_frame, d_max, total * 4, hipMemcpyDeviceToHost, e->stream));
+    CC_HIP_CHECK(e, hipStreamSynchronize(e->stream));
+    return CC_OK;
+}
+
+int cc_engine_scatter_apply(cc_engine* e, int stream, int64_t from, int64_t to, const int32_t* d_original_index, int slots, uint8_t* d_is_ground,
+                            uint32_t* d_detection, int64_t max_points)
+{
+    if (!e || stream < 0 || stream >= e->g.num_streams || slots < 1 || !d_original_index || !d_is_ground || !d_detection || max_points < 1 ||
+        from < 0 || to - from >= e->g.ring_cols)
+        return CC_ERR_INVALID_ARGUMENT;
+    if (to < from)
+        return CC_OK;
+    (void) hipSetDevice(e->device);
+    int rc = stop_resident(e);
+    if (rc)
+        return rc;
+    rc = finish_batch(e);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(cck::k_scatter_apply, dim3((unsigned) (to - from + 1)), dim3(64), 0, e->stream, e->g, e->P, (const StreamState*) e->d_states, stream, (long long) from,
+                       d_original_index, slots, d_is_ground, d_detection, (long long) max_points);
+    CC_HIP_CHECK(e, hipGetLastError());
+    return CC_OK; // (asynchronous on cc_engine_hip_stream(e): cc_eval_frame_device on the same stream, or cc_engine_sync, orders behind it)
+}
 
 int cc_replay_eval_create(cc_replay_eval** out, cc_engine* e, int slots, int64_t max_points, int eval_lanes)
 {

@@ -495,6 +495,51 @@ def test_take_clusters_between_pipelined_calls(pipeline, oracle_lib):
     e.close()
 
 
+# ---- 6b ---------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows", [32, 128])
+def test_cluster_records_are_the_point_takes_records(rows):
+    """The two hand-overs share one rule for a cell's return and id and one writer of the 32-byte record (cc_k_held.h): after three rotations on
+    two engines fed alike, one take_points(CLUSTERED, WITH_ID) and one take_clusters(1) must hold the same cells, keyed by (stream, global
+    column, row), with the same 32 bytes but for `column`, which counts from another origin. A partial trip of the row loop and two trips.
+    Clusters come out ahead of publication (test 4), so a cluster record in a column at or above the point take's col_to has no partner yet;
+    below it the match is one to one, in both directions."""
+    cols, NB, S = (256 if rows == 32 else 360), 3, 2
+    streams, cfg = _streams(rows, cols, NB, 9900 + rows, nan_last=False), _config(rows, cols)
+    e_pts, e_cl = _run_device(streams, cfg, NB), _run_device(streams, cfg, NB)
+    points, ptab = e_pts.take_points(CL, take.TAKE_WITH_ID)
+    clusters, crecords, ctab = e_cl.take_clusters(1)
+    pts, cl, crec = _host(points), _host_clusters(clusters), _host(crecords)
+    assert (ptab["error"] == 0).all() and (ctab["error"] == 0).all()
+    assert np.array_equal(ptab["lost_columns"], ctab["lost_columns"])        # (nobody took for three rotations: both start at the oldest column held)
+
+    def keyed(rec, stream, gcol):
+        """{(stream, global column, row): the record's bytes with `column` blanked}"""
+        rec = rec.copy()
+        rec["column"] = 0
+        raw = rec.view(np.uint8).reshape(-1, 32)
+        out = {(int(s), int(c), int(r)): raw[i].tobytes() for i, (s, c, r) in enumerate(zip(stream, gcol, rec["row"]))}
+        assert len(out) == len(rec)                                          # no key twice
+        return out
+
+    p_stream = np.repeat(np.arange(S), ptab["n_records"])
+    assert len(p_stream) == len(pts)
+    by_point = keyed(pts, p_stream, pts["column"].astype(np.int64) + ptab["col_from"][p_stream])
+    owner = np.repeat(np.arange(len(cl)), cl["n_points"].astype(np.int64))   # records are grouped by descriptor, no gaps (ClusterLog.add)
+    assert len(owner) == len(crec) and np.array_equal(crec["id"], cl["id"][owner])
+    by_cluster = keyed(crec, cl["stream"][owner], crec["column"].astype(np.int64) + cl["col_from"][owner])
+    for s in range(S):
+        to = int(ptab["col_to"][s])
+        published = {k: v for k, v in by_cluster.items() if k[0] == s and k[1] < to}
+        ahead = sum(1 for k in by_cluster if k[0] == s and k[1] >= to)
+        mine = {k: v for k, v in by_point.items() if k[0] == s}
+        print(f"rows {rows}, stream {s}: {len(published)} cluster records in published columns, {ahead} ahead of publication, {len(mine)} point records")
+        assert len(published) > 0
+        assert published.keys() == mine.keys(), (s, len(published), len(mine))
+        assert all(mine[k] == v for k, v in published.items()), s
+    e_pts.close()
+    e_cl.close()
+
+
 # ---- 7 ----------------------------------------------------------------------------------------------------------------------------------------
 def test_invalid_arguments_are_refused():
     import torch
