@@ -3,7 +3,8 @@
 // that places compacted output. Used by the id backlog (cc_k_publish.h), the takes (cc_k_take.h, cc_k_take_clusters.h), the frame scatter and the
 // replay evaluator (cc_k_replay_eval.h), and by the host's cursor queries (cc_take.h). DESIGN.md section 15.
 // (part of cc_kernels.h: included there, in order, inside namespace cck. The range rule is plain C++ without HIP types: a host-only program that
-// defines CC_HELD_RANGE_ONLY gets held_range and held_from alone — tests/csrc/held_range_probe.cpp)
+// defines CC_HELD_RANGE_ONLY gets held_range, held_from and the range of an image take, image_range, alone — tests/csrc/held_range_probe.cpp,
+// tests/csrc/image_range_probe.cpp)
 #pragma once
 
 #if defined(__HIPCC__)
@@ -40,6 +41,57 @@ CC_HELD_FN HeldRange held_range(const long long first_column, const long long cl
         r.from = r.to - ring_cols;          // (never: the ring holds no more)
     r.lost = r.from - base;
     return r;
+}
+
+// ---- the range of a reader that hands held columns over as whole rotations -----------------------------------------------------------------
+// For a reader that writes rotations of W columns into a ring of `slots` row-major images, rotation r into slot r % slots (no kernel does
+// yet: this is the range rule alone, checked by tests/test_take_images_cpu.py). Such a take writes whole columns [from, to): empty below
+// `readable_from`, from the engine's ring from there on.
+struct ImageRange
+{
+    long long from, to;                   // the columns [from, to) are written
+    long long readable_from;              // the first of them that comes from the ring (== to: none does)
+    long long lost;                       // HeldRange::lost
+    long long skipped;                    // readable columns dropped because the image ring holds `slots` rotations only
+    long long rotation_from, rotation_to; // the rotations [rotation_from, rotation_to) get their last column
+};
+
+// for a stream that has started, as held_range (one that has not yields an empty range at the cursor)
+CC_HELD_FN ImageRange image_range(const long long first_column, const long long clear_done, const long long upper, const long long cursor, const long long ring_cols,
+                                  const long long W, const long long slots)
+{
+    const HeldRange h = held_range(first_column, clear_done, upper, cursor, ring_cols);
+    const long long a0 = first_column / W * W; // (the first rotation's columns in front of the stream's first one never existed: written empty, not lost)
+    const long long c1 = cursor > a0 ? cursor : a0;
+    const long long rot_of_from = h.from / W * W; // (a rotation the cursor stands in is abandoned when clearing has reached a later one)
+    long long start = c1 > rot_of_from ? c1 : rot_of_from;
+    const long long oldest = (h.to / W - (slots - 1)) * W; // the image ring holds the rotation of h.to and slots - 1 before it
+    ImageRange r;
+    r.skipped = 0;
+    if (start < oldest)
+    {
+        const long long readable = start > h.from ? start : h.from;
+        r.skipped = oldest > readable ? oldest - readable : 0;
+        start = oldest;
+    }
+    r.from = start;
+    r.to = h.to;
+    r.readable_from = start > h.from ? start : h.from;
+    r.lost = h.lost;
+    r.rotation_from = start / W;
+    r.rotation_to = h.to / W > r.rotation_from ? h.to / W : r.rotation_from;
+    return r;
+}
+
+// of the columns [from, to) an image take writes, those inside rotation `rot`: how many, and how many of them are written empty because they
+// had been cleared (at or above the stream's first column, below readable_from)
+CC_HELD_FN void image_rotation_share(const ImageRange& r, const long long first_column, const long long rot, const long long W, long long* written, long long* lost)
+{
+    const long long lo = rot * W, hi = lo + W;
+    const long long a = r.from > lo ? r.from : lo, b = r.to < hi ? r.to : hi;
+    *written = b > a ? b - a : 0;
+    const long long la = a > first_column ? a : first_column, lb = b < r.readable_from ? b : r.readable_from;
+    *lost = lb > la ? lb - la : 0;
 }
 
 #ifndef CC_HELD_RANGE_ONLY
